@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py -- SSG-loss edge-pixels/sec (fwd+bwd) on MI355X.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c5] [--scaling weak|strong]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c5] [--scaling weak|strong] [--full] [--dump-outputs DIR]
 
 N > 1: either launched by `python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N`
 (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* from the env), or plain `python bench.py --gpus N`, which spawns the
@@ -15,7 +15,9 @@ SSG(gt) materialised once each, both criteria and d(l1+kl)/d sr.  Inputs are res
 edge pixel through that step.  Config c5 = BASELINE configs[4]: 1x3x512x512, dense mask,
 k_s = 49, k_w = 13 (one image per GPU).
 
-Prints ONE JSON line (rank 0) with the driver's fields plus
+A plain run sets up, pre-warms and warms up, times the K steps, writes the last step's outputs (--dump-outputs DIR)
+and prints ONE JSON line (rank 0) with the driver's fields.  Everything else it measures runs with --full only, whose
+line adds the times of two more K-step blocks, the shader clock after them and
   roofline      for the dominant kernel: algorithmic HBM bytes of the step (8 k_s^2 + (12C+4) HW/N per
                 edge pixel) x edge pixels per launch / that kernel's mean duration, measured here with HIP events
                 on the launch stream while the step's other launches are masked out (ssg_set_profile_mask of the profiling build
@@ -31,6 +33,11 @@ Prints ONE JSON line (rank 0) with the driver's fields plus
   module        the same step through the drop-in nn.Module (ssl_amd.SSGLoss: autograd forward + backward).
   cpu_baseline  the C/OpenMP oracle ("port") on the host cores over a bounded sample of the same workload
                 (rank 0, N = 1 only).
+
+--dump-outputs DIR (rank 0): what the timed step handed its caller after the last timed step, as DIR/<name>.npy --
+loss (l1, kl), grad (d(l1+kl)/d sr), counts (N, the first row of every image, N) and, when the step materialises
+the SSGs, a fixed seeded sample of their rows: ssg_sr, ssg_gt, with ssg_rows (row numbers) and ssg_edges (their
+edge-list entries).  The inputs are seeded, so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -699,6 +706,31 @@ def step_share_lines(dev):
     return out
 
 
+DUMP_SSG_BYTES = 16 << 20      # sampled SSG rows per tensor: with the gradient a dump stays well under 64 MB
+
+
+def dump_outputs(step, out_dir):
+    """The last step's outputs as float32 / float64 .npy files (see the module docstring)."""
+    import numpy as np
+    import torch
+    torch.cuda.synchronize()
+    out = {"loss": step.loss.cpu().numpy(), "grad": step.grad.cpu().numpy(),
+           "counts": step.counts.cpu().numpy().astype(np.float64)}
+    if step.materialise:
+        n = min(int(out["counts"][0]), step.capacity)
+        k = min(n, DUMP_SSG_BYTES // (4 * step.ssg_sr.shape[1]))
+        rows = np.sort(np.random.default_rng(0).choice(n, k, replace=False))
+        idx = torch.as_tensor(rows, device=step.grad.device)
+        out["ssg_rows"] = rows.astype(np.float64)
+        out["ssg_edges"] = step.edges()[idx].cpu().numpy().astype(np.float64)
+        out["ssg_sr"] = step.ssg_sr[idx].cpu().numpy()
+        out["ssg_gt"] = step.ssg_gt[idx].cpu().numpy()
+    assert sum(a.nbytes for a in out.values()) <= 64 << 20
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def make_inputs(cfg, rank, world, scaling):
     """Synthetic batch of this rank (numpy): weak = `batch` images per rank, strong = the rank's share of ONE batch."""
     import numpy as np
@@ -735,6 +767,11 @@ def main():
     ap.add_argument("--config", choices=sorted(CONFIGS), default="c2")
     ap.add_argument("--scaling", choices=("weak", "strong"), default="weak",
                     help="weak: 16 images per GPU; strong: the 16 images split over the GPUs (SURVEY 8e)")
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything beside the headline as well: more timing blocks, shader clock, roofline and "
+                         "per-kernel table, module, `extra`, CPU baseline (the --no-* switches below trim this run)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the outputs of the last timed step to DIR/<name>.npy (rank 0)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-prewarm", action="store_true", help="skip the timed pre-warm before the W warm-up steps")
     ap.add_argument("--no-module", action="store_true", help="skip the SSGLoss (nn.Module) timing")
@@ -753,6 +790,8 @@ def main():
     ap.add_argument("--dry-run", action="store_true", help="no GPU work: exercise the launcher / sharding / "
                     "reduction plumbing on CPU with the gloo backend (used by the CPU test-suite)")
     args = ap.parse_args()
+    if args.dump_outputs and args.dry_run:
+        ap.error("--dump-outputs needs the GPU step (not --dry-run)")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if args.gpus > 1 and "RANK" not in os.environ:
@@ -841,11 +880,13 @@ def main():
             last_blk = blk
     prewarm_ms = (time.perf_counter() - prewarm_t0) * 1e3 if prewarm_steps else 0.0
     elapsed = timed_round()
+    if args.dump_outputs and rank == 0 and step is not None:
+        dump_outputs(step, args.dump_outputs)
 
     # two more blocks of the same K steps, for information only (`config.ms_per_step_blocks`): the first entry is the
     # timed region above; a clock still ramping after the warm-up shows up as a first block slower than the others
     blocks = [elapsed / max(args.steps, 1) * 1e3]
-    if not args.dry_run and world == 1:
+    if args.full and not args.dry_run and world == 1:
         for _ in range(2):
             sync_all()
             tb = time.perf_counter()
@@ -888,12 +929,13 @@ def main():
                        "input_checksum": synth.checksum(sr_np, gt_np, mask_np),
                        "gradient_accumulation": "fixed-point integer atomics (bit-reproducible, the shipped default)",
                        "prewarm_steps": prewarm_steps, "prewarm_ms": prewarm_ms, "prewarm_block_ms_per_step": prewarm_blocks,
-                       "ms_per_step_blocks": blocks,
-                       "ms_per_step_block2": blocks[1] if len(blocks) > 1 else None,
-                       "ms_per_step_block3": blocks[2] if len(blocks) > 2 else None,
-                       "sclk_after_timed_region": gpu_clock(),
                        "parallelism": f"images sharded x{world}, no data-path collective"},
         }
+        if args.full:
+            res["config"].update({"ms_per_step_blocks": blocks,
+                                  "ms_per_step_block2": blocks[1] if len(blocks) > 1 else None,
+                                  "ms_per_step_block3": blocks[2] if len(blocks) > 2 else None,
+                                  "sclk_after_timed_region": gpu_clock()})
         if args.dry_run:
             res["dry_run"] = True
             res["value"] = None
@@ -901,6 +943,7 @@ def main():
             assert int(step.counts[0]) == n_edges
             loss = step.loss.cpu().numpy()
             res["config"]["l1"], res["config"]["kl"] = float(loss[0]), float(loss[1])
+        if args.full and step is not None:
             b_alg = alg_bytes_per_edge_px(cfg, n_edges, B) - (8.0 * cfg["ks"] ** 2 if args.no_ssg_output else 0.0)
             it = max(3, min(args.steps, 10))
             # The per-kernel table launches the kernels one at a time through the separate entry points.  It is skipped

@@ -8,7 +8,7 @@ if [ -n "$sel" ]; then
   timeout 900 python -m pytest tests -m gpu -x -q --timeout 600 -k "$sel" > "$O/pytest.txt" 2>&1; echo "pytest rc=$?"; tail -3 "$O/pytest.txt"
 fi
 steps=50; [ "$cfg" = c5 ] && steps=10
-python bench.py --config $cfg --steps $steps --warmup 5 --no-cpu-baseline > "$O/bench_$cfg.json" 2> "$O/bench_$cfg.err" || tail -5 "$O/bench_$cfg.err"
+python bench.py --full --config $cfg --steps $steps --warmup 5 --no-cpu-baseline > "$O/bench_$cfg.json" 2> "$O/bench_$cfg.err" || tail -5 "$O/bench_$cfg.err"
 python - "$O/bench_$cfg.json" <<'PY'
 import json, sys
 d = json.load(open(sys.argv[1]))

@@ -4,7 +4,7 @@ cd "${GRAFT_REPO_ROOT:-.}" || exit 1
 R="$PWD"; O="$R/gpurun_out/r4_c5f_icache"; rm -rf "$O"; mkdir -p "$O"; export TMPDIR=/tmp; cd /tmp
 export SSG_OVERLAP=0
 for set in "SQC_ICACHE_REQ SQC_ICACHE_HITS SQC_ICACHE_MISSES SQC_ICACHE_MISSES_DUPLICATE SQ_IFETCH SQ_WAVE_CYCLES SQ_WAIT_INST_ANY SQ_INSTS_VALU"; do
-  timeout 600 rocprofv3 --pmc $set --kernel-trace --output-format csv -d "$O/p" -o pmc -- python "$R/bench.py" --config ${1:-c5} ${2:---no-ssg-output} --no-kernel-table --steps 3 --warmup 1 --no-cpu-baseline --no-module --no-extra > "$O/p.log" 2>&1
+  timeout 600 rocprofv3 --pmc $set --kernel-trace --output-format csv -d "$O/p" -o pmc -- python "$R/bench.py" --full --config ${1:-c5} ${2:---no-ssg-output} --no-kernel-table --steps 3 --warmup 1 --no-cpu-baseline --no-module --no-extra > "$O/p.log" 2>&1
   find "$O/p" -name "*kernel_trace.csv" -delete
   python - "$O/p" <<'PY'
 import csv, sys, glob, collections

@@ -3,7 +3,7 @@
 cd "${GRAFT_REPO_ROOT:-.}" || exit 1
 O=gpurun_out/r4c; mkdir -p $O
 timeout 2400 python -m pytest tests -m gpu -q --timeout 900 > $O/pytest.txt 2>&1; echo "pytest rc=$?"; grep -n "^FAILED\|passed\|failed\|^E " $O/pytest.txt | head -20
-python bench.py > $O/bench_c2.json 2> $O/bench_c2.err; echo "bench rc=$?"
+python bench.py --full > $O/bench_c2.json 2> $O/bench_c2.err; echo "bench rc=$?"
 python - <<'PY'
 import json
 d = json.load(open("gpurun_out/r4c/bench_c2.json"))

@@ -9,7 +9,7 @@ for c in b1 b4 c4; do
   done
 done | tee $O/times.txt
 for m in 0 auto; do
-  if [ $m = auto ]; then python bench.py --no-extra --no-cpu-baseline --no-module --steps 100 --warmup 20; else SSG_FWD_CSPLIT=$m python bench.py --no-extra --no-cpu-baseline --no-module --steps 100 --warmup 20; fi 2>/dev/null | python -c "
+  if [ $m = auto ]; then python bench.py --full --no-extra --no-cpu-baseline --no-module --steps 100 --warmup 20; else SSG_FWD_CSPLIT=$m python bench.py --full --no-extra --no-cpu-baseline --no-module --steps 100 --warmup 20; fi 2>/dev/null | python -c "
 import sys, json
 d = json.loads(sys.stdin.read()); k = d['roofline']['kernel_ms']
 print('c2 csplit=$m step %.4f' % d['ms_per_step'], ' '.join('%s %.3f' % (n.split('<')[0].replace('ssg_', ''), v) for n, v in k.items()))"

@@ -5,10 +5,10 @@ cd "${GRAFT_REPO_ROOT:-.}" || exit 1
 R="$PWD"; O="$R/gpurun_out/r4a"; rm -rf "$O"; mkdir -p "$O"; export TMPDIR=/tmp
 timeout 900 python -m pytest tests/test_gpu_ref_api.py -m gpu -q --timeout 600 > "$O/pytest_ref_api.txt" 2>&1; echo "pytest ref_api rc=$?"; tail -15 "$O/pytest_ref_api.txt"
 timeout 1500 python -m pytest tests -m gpu -x -q --timeout 900 --deselect tests/test_gpu_ref_api.py > "$O/pytest_all.txt" 2>&1; echo "pytest all rc=$?"; tail -5 "$O/pytest_all.txt"
-python bench.py > "$O/r4_bench_c2.json" 2> "$O/bench_c2.err"; echo "bench c2 rc=$?"; tail -3 "$O/bench_c2.err"
-python bench.py --config c4 --no-extra > "$O/r4_bench_c4.json" 2> "$O/bench_c4.err"; echo "bench c4 rc=$?"; tail -3 "$O/bench_c4.err"
+python bench.py --full > "$O/r4_bench_c2.json" 2> "$O/bench_c2.err"; echo "bench c2 rc=$?"; tail -3 "$O/bench_c2.err"
+python bench.py --full --config c4 --no-extra > "$O/r4_bench_c4.json" 2> "$O/bench_c4.err"; echo "bench c4 rc=$?"; tail -3 "$O/bench_c4.err"
 cd /tmp
-SSG_OVERLAP=0 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/prof_c4" -o bench -- python "$R/bench.py" --config c4 --steps 20 --warmup 3 --no-cpu-baseline --no-module --no-extra --no-kernel-table > "$O/prof_c4.log" 2>&1
+SSG_OVERLAP=0 rocprofv3 --kernel-trace --stats --output-format csv -d "$O/prof_c4" -o bench -- python "$R/bench.py" --full --config c4 --steps 20 --warmup 3 --no-cpu-baseline --no-module --no-extra --no-kernel-table > "$O/prof_c4.log" 2>&1
 f=$(find "$O/prof_c4" -name "*kernel_stats.csv" | head -1); [ -n "$f" ] && cp "$f" "$O/r4_bench_c4_kernel_stats.csv"
 find "$O/prof_c4" -name "*kernel_trace.csv" -delete
 cd "$R"

@@ -14,7 +14,7 @@ for c in b1 c4 c1; do
   echo "== $c"; cut -d, -f1-4 "$O/r4_sparse_${c}_kernel_stats.csv" | head -24
 done
 cd "$R"
-python bench.py --no-extra --no-cpu-baseline --steps 50 --warmup 10 > "$O/bench_c2.json" 2>/dev/null
+python bench.py --full --no-extra --no-cpu-baseline --steps 50 --warmup 10 > "$O/bench_c2.json" 2>/dev/null
 python - <<'PY'
 import json
 d = json.load(open("gpurun_out/r4s/bench_c2.json"))

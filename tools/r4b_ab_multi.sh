@@ -5,7 +5,7 @@ mkdir -p gpurun_ab/work gpurun_out/r4b; cp ssl_amd/csrc/libssg_hip*.so gpurun_ab
 for rep in 1 2 3; do
   for t in "$@"; do
     cp gpurun_ab/$t/libssg_hip.so gpurun_ab/$t/libssg_hip_prof.so ssl_amd/csrc/
-    python bench.py --no-cpu-baseline --no-module --no-extra --steps 100 --warmup 20 2>/dev/null | python -c "
+    python bench.py --full --no-cpu-baseline --no-module --no-extra --steps 100 --warmup 20 2>/dev/null | python -c "
 import sys, json
 d = json.loads(sys.stdin.read()); k = d['roofline'].get('kernel_ms', {})
 print('%-6s' % '$t', 'c2 %.4f' % d['ms_per_step'], ' '.join('%s %.3f' % (n.split('<')[0].split(' (')[0].replace('ssg_', ''), v) for n, v in k.items()))"

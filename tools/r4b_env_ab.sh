@@ -4,7 +4,7 @@ cd "${GRAFT_REPO_ROOT:-.}" || exit 1
 mkdir -p gpurun_out/r4b
 for rep in 1 2 3; do
   for e in "$@"; do
-    env $e python bench.py --no-cpu-baseline --no-module --no-extra --steps 100 --warmup 20 2>/dev/null | python -c "
+    env $e python bench.py --full --no-cpu-baseline --no-module --no-extra --steps 100 --warmup 20 2>/dev/null | python -c "
 import sys, json
 d = json.loads(sys.stdin.read()); k = d['roofline'].get('kernel_ms', {})
 print('%-34s' % '$e', 'c2 step %.4f' % d['ms_per_step'], ' '.join('%s %.3f' % (n.split('<')[0].split(' (')[0].replace('ssg_', ''), v) for n, v in k.items() if n.startswith('edge') or 'all' in n))"

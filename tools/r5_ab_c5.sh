@@ -11,7 +11,7 @@ for rep in 1 2; do
     for m in mat fused; do
       [ $what != both ] && [ $what != $m ] && continue
       fl="--config c5 --no-kernel-table --steps 10 --warmup 3 --no-cpu-baseline --no-module --no-extra"; [ $m = fused ] && fl="$fl --no-ssg-output"
-      rm -rf $O/p; rocprofv3 --kernel-trace --stats --output-format csv -d $O/p -o p -- python bench.py $fl > $O/$t.json 2> $O/$t.err
+      rm -rf $O/p; rocprofv3 --kernel-trace --stats --output-format csv -d $O/p -o p -- python bench.py --full $fl > $O/$t.json 2> $O/$t.err
       f=$(find $O/p -name "*kernel_stats.csv" | head -1)
       echo "$t $m step $(grep -o '"ms_per_step": [0-9.]*' $O/$t.json | head -1 | cut -d' ' -f2 | cut -c1-6) $(head -4 "$f" | python -c "
 import sys, csv

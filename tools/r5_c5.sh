@@ -13,7 +13,7 @@ fi
 [ "$mode" = testonly ] && exit 0
 for m in mat fused; do
   fl="--config c5 --no-kernel-table --steps 10 --warmup 3 --no-cpu-baseline --no-module --no-extra"; [ $m = fused ] && fl="$fl --no-ssg-output"
-  rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_${tag}_$m -o p -- python bench.py $fl > $O/${tag}_$m.json 2> $O/${tag}_$m.err
+  rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_${tag}_$m -o p -- python bench.py --full $fl > $O/${tag}_$m.json 2> $O/${tag}_$m.err
   f=$(find $O/prof_${tag}_$m -name "*kernel_stats.csv" | head -1)
   echo "== $tag $m: $(grep -o '"ms_per_step": [0-9.]*' $O/${tag}_$m.json | head -1)"
   head -5 "$f" | python -c "

@@ -4,7 +4,7 @@ cd "${GRAFT_REPO_ROOT:-.}" || exit 1
 O=gpurun_out/r5c; mkdir -p $O
 timeout 2400 python -m pytest tests -m gpu -q --timeout 900 > $O/pytest.txt 2>&1; echo "pytest rc=$?"; grep -n "^FAILED\|passed\|failed\|^E " $O/pytest.txt | head -20
 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.txt 2>&1; echo "smoke rc=$?"; tail -2 $O/smoke.txt
-python bench.py > $O/bench_c2.json 2> $O/bench_c2.err; echo "bench rc=$?"; tail -3 $O/bench_c2.err
+python bench.py --full > $O/bench_c2.json 2> $O/bench_c2.err; echo "bench rc=$?"; tail -3 $O/bench_c2.err
 python - <<'PY'
 import json
 d = json.load(open("gpurun_out/r5c/bench_c2.json"))

@@ -11,7 +11,7 @@ for set in "SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_INSTS_LDS SQ
            "SQ_INSTS_VMEM_WR SQ_INSTS_VMEM_RD SQ_ACTIVE_INST_VMEM SQ_ACTIVE_INST_SCA SQ_ACTIVE_INST_MISC SQ_INST_CYCLES_VMEM SQ_INSTS_BRANCH" \
            "GRBM_GUI_ACTIVE GRBM_COUNT"; do
   i=$((i+1))
-  timeout 600 rocprofv3 --pmc $set --kernel-trace --output-format csv -d $O/p$i -o pmc -- python bench.py $flags --steps 3 --warmup 1 --no-cpu-baseline --no-module --no-extra --no-kernel-table > $O/p$i.log 2>&1
+  timeout 600 rocprofv3 --pmc $set --kernel-trace --output-format csv -d $O/p$i -o pmc -- python bench.py --full $flags --steps 3 --warmup 1 --no-cpu-baseline --no-module --no-extra --no-kernel-table > $O/p$i.log 2>&1
   echo "pass $i rc=$?"
 done
 python - "$O" "$filt" <<'PY'

@@ -12,8 +12,8 @@ for rep in $(seq 1 ${REPS:-3}); do
     if [ $rep = 1 ] && [ -n "$tests" ] && [ $t != work ]; then
       timeout 900 python -m pytest tests/test_gpu_parity.py -m gpu -x -q -k "$tests" 2>&1 | tail -1 | sed "s/^/$t tests: /" | tee -a $out
     fi
-    c2=$(python bench.py --no-cpu-baseline --no-module --no-extra --no-kernel-table --steps 100 --warmup 20 2>/dev/null | grep -o '"ms_per_step": [0-9.]*' | head -1 | cut -d' ' -f2 | cut -c1-6)
-    k=$(python bench.py --no-cpu-baseline --no-module --no-extra --steps 20 --warmup 5 2>/dev/null | python -c "
+    c2=$(python bench.py --full --no-cpu-baseline --no-module --no-extra --no-kernel-table --steps 100 --warmup 20 2>/dev/null | grep -o '"ms_per_step": [0-9.]*' | head -1 | cut -d' ' -f2 | cut -c1-6)
+    k=$(python bench.py --full --no-cpu-baseline --no-module --no-extra --steps 20 --warmup 5 2>/dev/null | python -c "
 import sys, json
 d = json.loads(sys.stdin.read()); k = d['roofline'].get('kernel_ms', {})
 print(' '.join('%s %.3f' % (n.split('<')[0].replace('ssg_', '') + ('+' if 'merged' in n else ''), v) for n, v in k.items() if n.startswith('ssg_') or n.startswith('edge') or 'all' in n))")

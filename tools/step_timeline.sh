@@ -4,7 +4,7 @@
 cd "${GRAFT_REPO_ROOT:-.}" || exit 1
 R="$PWD"; cfg="${1:-c2}"; O="$R/gpurun_out/timeline_$cfg"; rm -rf "$O"; mkdir -p "$O"; export TMPDIR=/tmp
 cd /tmp
-rocprofv3 --kernel-trace --memory-copy-trace --output-format csv -d "$O" -o tl -- python "$R/bench.py" --config $cfg --steps 6 --warmup 3 --no-cpu-baseline --no-module --no-extra > "$O/log.txt" 2>&1
+rocprofv3 --kernel-trace --memory-copy-trace --output-format csv -d "$O" -o tl -- python "$R/bench.py" --full --config $cfg --steps 6 --warmup 3 --no-cpu-baseline --no-module --no-extra > "$O/log.txt" 2>&1
 cd "$R"
 python - "$O" <<'PY'
 import csv, glob, sys
