@@ -165,13 +165,13 @@ int ssg_set_dense_threshold(int edge_pixels_per_tile);
  * caller's stream; capturable).  0: every launch on the caller's stream (per-kernel profiling).  1: the dense-tile
  * kernel on the caller's stream, the direct kernel beside it on the side stream -- for masks whose dense tiles carry
  * most rows (Laplacian edge masks).  2: the other way round -- for masks without dense tiles (Bernoulli, thin strided
- * masks: the whole critical path on one stream; Bernoulli 1 % -15 %, C2 +3 %).  3 (default): 1 or 2 per pass, by the
+ * masks: the whole critical path on one stream; Bernoulli 1 % -15 %, C2 +3 %).  3 (default): 1 or 2 per call, by the
  * shape of the last plan ssg_edge_list / the fused step built on the device -- its scan kernel leaves {rows for the
  * direct kernels, dense tiles} in host-mapped memory, the host reads it at the next pass without synchronising; the
  * branch expected to take longer (38 ns per direct row against 0.74 us per dense tile) stays on the caller's stream.
  * In mode 3 the fused steps (ssg_loss_fwd_bwd, ssg_loss_step) also run forward AND backward of the two branches as two
  * chains with ONE join at the end: free-running when the direct chain carries the step or the plan holds at most 512
- * dense tiles, otherwise with the direct backward held by a one-way event until the dense backward starts (C2 1.27 ->
+ * dense tiles, otherwise with the direct backward held by a one-way event until the dense forward is through (C2 1.27 ->
  * 1.25 ms, C4 0.50 -> 0.46, Bernoulli 1 % 0.185 -> 0.175).
  * Same results, bit for bit in deterministic mode, in every mode and schedule (disjoint rows, integer sums at a scale that
  * does not depend on the schedule).  Process-wide; returns the previous setting.  No reference counterpart (the

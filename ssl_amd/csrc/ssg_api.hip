@@ -14,8 +14,7 @@ int launch_fwd(const FwdParams &p, hipStream_t st);
 int launch_bwd(const BwdParams &p, hipStream_t st);
 unsigned bwd_grid(const BwdParams &p);
 size_t bwd_max_partials(int B, int H, int W, int n_rows);
-int launch_loss_finalize(const float *partials, int nparts, const int *n_dev, int n_host, int P, float w_l1,
-                         float w_kl, float *loss_out, int nan_on_overflow, hipStream_t st, int set_size = 0);
+int launch_loss_finalize(const LossFinalize &f, hipStream_t st);
 const char *fwd_kernel_name(int ks, int kw);
 const char *bwd_kernel_name(int ks, int kw);
 size_t edge_scratch_bytes(int B, int H, int W);
@@ -178,7 +177,7 @@ static constexpr int dbg_mask() { return 0; }
 // The dense-tile kernel and the direct kernel of a pass work on disjoint SSG rows (and add into the gradient with
 // atomics), so the direct one runs on a side stream beside the dense one: fork = side waits for an event on the
 // caller's stream, join = the caller's stream waits for the side's event.  Both are plain event edges, so a stream
-// capture of the caller's stream (hipGraph) records the fork as two parallel branches.  One side stream and three
+// capture of the caller's stream (hipGraph) records the fork as two parallel branches.  One side stream and four
 // events per (host thread, device); ssg_set_overlap(0) keeps every launch on the caller's stream.  Measured on MI355X:
 // C2 (k_s 25) 1.541 -> 1.510 ms per step; C5 (k_s 49, every kernel already fills the chip for its whole run)
 // 9.15 -> 9.64 ms -- so the fork is taken for k_s <= 25 only.
@@ -198,23 +197,16 @@ static int overlap_mode() {
   }
   return v;
 }
-static bool overlap_enabled() { return overlap_mode() != 0; }
-// Schedules of a fused step at k_s <= 25 (ForkChain below).  FREE-RUNNING chains pay when the direct chain carries the
-// step (Bernoulli 4 %: 0.485 -> 0.463 ms) or the dense kernels are too few workgroups to keep the chip to themselves
-// (C4, 330 tiles: 0.50 -> 0.466).  Where long dense kernels dominate (C2: 1,287 tiles, direct 0.38 ms of kernel time
-// against 0.95) free-running direct kernels spend themselves beside the dense FORWARD and the dense backward runs alone
-// with its tail unfilled (+8 %); there the chains are GATED -- the direct backward waits, one way, for the dense chain's
-// row pass (C2 1.271 -> 1.248 against fork / join around each pass; a low-priority side stream: no effect).
-// two_chains_wanted(): free-running (true) or gated (false), per call from the last plan's shape (PlanHint: the numbers
-// the stream assignment uses); unknown = gated.
-// (profiling build: SSG_TWO_CHAINS=0 always gated, 2 always free-running, -1 no chains: fork / join around each pass)
-static bool two_chains_wanted();
-static bool two_chains_allowed();
+
+static bool stream_capturing(hipStream_t st) {
+  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+  return hipStreamIsCapturing(st, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone;
+}
 
 // What the last plan built on a device looked like: {rows left to the direct kernels, dense tiles}, written by the
 // edge-list builder's scan kernel with a plain store into host-mapped pinned memory (one 64-byte block per device,
-// allocated at the first build, never freed; a posted PCIe write, no stream operation) and read by the HOST at the next
-// forked pass -- no synchronisation: whatever has landed is a hint, and both stream assignments give the same results.
+// allocated at the first build, never freed; a posted PCIe write, no stream operation) and read by the HOST once per
+// call (schedule() below) -- no synchronisation: whatever has landed is a hint, and every schedule gives the same results.
 struct PlanHint {
   int *host = nullptr, *dev = nullptr;
 };
@@ -241,72 +233,73 @@ static PlanHint plan_hint(bool allocate_never = false) {
   }
   return tab[dev];
 }
-// rows the last plan built on this device left to the direct kernels (-> FwdParams / BwdParams::rows_hint); 0 = unknown
-static int hint_sparse_rows() {
-  if (overlap_mode() != 3) return 0;
-  const PlanHint h = plan_hint(true);
-  if (!h.host) return 0;
-  const int n = ((volatile int *)h.host)[0];
-  return n > 0 ? n : 0;
-}
 namespace ssg {
 int *plan_hint_device_word(hipStream_t st) {
   if (overlap_mode() != 3) return nullptr;
-  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-  const bool capturing = hipStreamIsCapturing(st, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone;
-  return plan_hint(capturing).dev;
+  return plan_hint(stream_capturing(st)).dev;
 }
 }
-// the two streams of a forked pass: .dense takes the dense-tile kernel, .direct the direct one
-struct StreamPair {
-  hipStream_t dense, direct;
+
+// The schedule of one entry-point call: which stream takes the dense-tile kernels and which the direct ones, and -- in
+// a fused step or a loss backward at k_s <= 25 -- whether the two classes run as two CHAINS.  The dense-tile chain
+// (forward, its rows' ssg_grad_rows pass, backward) and the direct chain (the same three for the rows of the plan's
+// sparse list) then share nothing until ONE join at the end: the row passes are per class anyway (split_backward), the
+// fixed-point scale of the deterministic accumulation comes from the a-priori bound of |G| (no maximum over all rows to
+// wait for), integer sums do not care who adds first, the criteria sums go to separate slots.  Same bits as fork / join
+// around each pass -- only the streams differ -- with one cross-stream round trip less, and the memory-bound row pass of
+// one chain runs beside the VALU-bound kernels of the other.
+// FREE-RUNNING chains pay when the direct chain carries the step (Bernoulli 4 %: 0.485 -> 0.463 ms) or the dense kernels
+// are too few workgroups to keep the chip to themselves (C4, 330 tiles: 0.50 -> 0.466).  Where long dense kernels
+// dominate (C2: 1,287 tiles, direct 0.38 ms of kernel time against 0.95) free-running direct kernels spend themselves
+// beside the dense FORWARD and the dense backward runs alone with its tail unfilled (+8 %); there the chains are GATED:
+// the direct backward waits, one way, for the dense chain (split_backward; C2 1.271 -> 1.248 against fork / join around
+// each pass; a low-priority side stream: no effect).
+struct Schedule {
+  hipStream_t st = nullptr;     // the caller's stream
+  bool may_fork = false;        // k_s <= 25, and overlap not off (ssg_set_overlap(0))
+  int assign = 0;               // 1: dense-tile kernels on st, direct ones on the side stream; 2: the other way round
+  bool chains = false;          // two chains: the forward's fork stays open for the backward (or it opens at the row passes)
+  bool gated = false;           // ... with the direct backward held behind the dense forward (dense chain on st)
+  int rows_hint = 0;            // rows the last plan left to the direct kernels (FwdParams / BwdParams::rows_hint); 0 unknown
+  SideStream *side = nullptr;   // (fork_side)
+  bool open = false;            // forked, not yet joined
+  hipStream_t dense() const { return open && assign == 2 ? side->side : st; }
+  hipStream_t direct() const { return open && assign == 1 ? side->side : st; }
 };
-static thread_local int t_last_assignment = 0;
-static StreamPair assign_streams(hipStream_t st, hipStream_t st2) {
-  int mode = overlap_mode();
+
+// One read of the overlap mode, of the plan hint and (where it decides) of the capture state per call: the hint is
+// written by the GPU asynchronously, and decisions taken from two reads could disagree (a flip between them could record
+// a gated pair into a capturing stream).  `chains`: the call can run two chains (a fused step with a gradient and a plan;
+// a loss backward, whose split_backward checks the rest).
+static Schedule schedule(hipStream_t st, int ks, bool chains) {
+  Schedule s;
+  s.st = st;
+  const int mode = overlap_mode();
+  int n_sparse = -1, n_tiles = -1;
   if (mode == 3) {
-    // whole-chip costs at (25,9), MI355X: a dense tile 0.74 us through forward + backward, a direct row 38 ns
-    mode = 1;
     const PlanHint h = plan_hint(true);   // (readers never allocate: the builder's launch does, outside capture)
     if (h.host) {
-      const int n_sparse = ((volatile int *)h.host)[0], n_tiles = ((volatile int *)h.host)[1];
-      if (n_sparse >= 0 && n_tiles >= 0 && (long long)n_sparse * 38 > (long long)n_tiles * 740) mode = 2;
+      n_sparse = ((volatile int *)h.host)[0];
+      n_tiles = ((volatile int *)h.host)[1];
     }
   }
-  t_last_assignment = st2 == st ? 0 : mode;
-  return mode == 2 ? StreamPair{st2, st} : StreamPair{st, st2};
+  const bool known = n_sparse >= 0 && n_tiles >= 0;
+  // whole-chip costs at (25,9), MI355X: a dense tile 0.74 us through forward + backward, a direct row 38 ns
+  const bool direct_longer = known && (long long)n_sparse * 38 > (long long)n_tiles * 740;
+  s.assign = mode == 3 ? (direct_longer ? 2 : 1) : mode;
+  s.rows_hint = n_sparse > 0 ? n_sparse : 0;
+  s.may_fork = ks <= 25 && mode != 0;
+  // free-running: the direct chain carries the step, or the dense kernels' grids (two images per tile) are at most two
+  // resident rounds of 512 workgroups -- too short to keep the chip to themselves anyway; no hint = gated
+  const bool free = mode == 3 && known && (direct_longer || n_tiles <= 512);
+  // (under stream capture only free-running chains: they replay well -- C4 0.452 ms as a graph, 0.495 joined --, a
+  // GATED pair does not: C2 as a graph 1.44 ms gated, 1.26 with fork / join around each pass, which it keeps)
+  s.chains = chains && s.may_fork && (free || !stream_capturing(st));
+  s.gated = !free && s.assign == 1;   // (dense chain on the side stream -- a forced ssg_set_overlap(2): free-running)
+  return s;
 }
-// Gated chains, round 6: the direct backward is released when the dense FORWARD is through (not, as in round 5, the dense
-// chain's row pass): it then runs beside that memory-bound row pass -- C2 1.1996 -> 1.178 ms, three alternations
-// (profiles/r6_schedule_ab.txt; holding the direct FORWARD until the dense forward is through as well: 1.184 alone,
-// 1.20 together).  The loss finalize follows the direct backward on its stream, behind a second event for the dense
-// chain's row pass.  (profiling build: SSG_SCHED=1 restores the round-5 gate.)
-static int sched_mode() {
-  static const int m = env_int("SSG_SCHED", 0);
-  return m;
-}
-static bool two_chains_allowed() {   // (profiling build: SSG_TWO_CHAINS=-1 restores fork / join around forward and backward each)
-  static const bool on = env_int("SSG_TWO_CHAINS", 1) >= 0;
-  return on;
-}
-// (a stream that is being captured into a HIP graph: free-running chains replay well -- C4 0.452 ms as a graph, 0.495
-// joined --, a GATED pair does not: C2 as a graph 1.44 ms gated, 1.26 with fork / join around each pass, which it keeps)
-static bool stream_capturing(hipStream_t st) {
-  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-  return hipStreamIsCapturing(st, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone;
-}
-static bool two_chains_wanted() {    // free-running (true) or gated (false)
-  static const int sw = env_int("SSG_TWO_CHAINS", 1);
-  if (sw != 1) return sw == 2;
-  if (overlap_mode() != 3) return false;
-  const PlanHint h = plan_hint(true);
-  if (!h.host) return false;
-  const int n_sparse = ((volatile int *)h.host)[0], n_tiles = ((volatile int *)h.host)[1];
-  if (n_sparse < 0 || n_tiles < 0) return false;
-  // the direct chain carries the step, or the dense kernels' grids (two images per tile) are at most two resident rounds
-  // of 512 workgroups: too short to keep the chip to themselves anyway
-  return (long long)n_sparse * 38 > (long long)n_tiles * 740 || n_tiles <= 512;
-}
+
+static thread_local int t_last_assignment = 0;
 // (diagnostics: the assignment the calling thread's last forked pass used -- 0 none, 1 dense-tile kernel on the caller's
 // stream, 2 direct kernel on the caller's stream)
 extern "C" int ssg_last_overlap_assignment(void) { return t_last_assignment; }
@@ -317,7 +310,7 @@ extern "C" int ssg_last_overlap_assignment(void) { return t_last_assignment; }
 // critical path then sits on one stream and whose join finds the side stream's empty launches finished.  Measured on one
 // box (profiles/r5_ab_stream_assignment.txt): mode 2 against 1: Bernoulli 1 % 0.213 -> 0.182 ms, 4 % 0.491 -> 0.466,
 // C4 0.498 -> 0.508, C2 1.275 -> 1.317 (the fork's latency lands on whichever kernel runs on the side stream).
-// 3 (default since round 5): 1 or 2 per pass, from the shape of the last plan built on the device (PlanHint above): the
+// 3 (default since round 5): 1 or 2 per call, from the shape of the last plan built on the device (PlanHint above): the
 // branch expected to run longer stays on the caller's stream.  Steady streams of similar masks settle after one call.
 // Returns the previous setting.
 extern "C" int ssg_set_overlap(int mode) {
@@ -329,7 +322,7 @@ static SideStream *side_stream() {
   constexpr int MAXDEV = 64;
   thread_local SideStream tab[MAXDEV];
   int dev = 0;
-  if (!overlap_enabled() || hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= MAXDEV) return nullptr;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= MAXDEV) return nullptr;
   SideStream &s = tab[dev];
   if (!s.side) {
     if (hipStreamCreateWithFlags(&s.side, hipStreamNonBlocking) != hipSuccess ||
@@ -343,40 +336,21 @@ static SideStream *side_stream() {
   }
   return &s;
 }
-// stream for the second branch after everything queued on `st` so far (st itself when overlap is off)
-static hipStream_t fork_from(hipStream_t st, int ks, SideStream *&s) {
-  s = ks <= 25 ? side_stream() : nullptr;
-  if (!s) return st;
-  if (hipEventRecord(s->forked, st) != hipSuccess || hipStreamWaitEvent(s->side, s->forked, 0) != hipSuccess) {
-    s = nullptr;
-    return st;
-  }
-  return s->side;
+// Fork at a pass that can fork: the side stream takes what follows after everything queued on the caller's so far (no
+// fork: every launch on the caller's stream; `skip`, profiling build: a launch of the pass is masked out).
+static void fork_side(Schedule &s, bool skip = false) {
+  s.side = s.may_fork && !skip ? side_stream() : nullptr;
+  s.open = s.side && hipEventRecord(s.side->forked, s.st) == hipSuccess &&
+           hipStreamWaitEvent(s.side->side, s.side->forked, 0) == hipSuccess;
+  t_last_assignment = s.open ? s.assign : 0;
 }
-static int join_to(hipStream_t st, SideStream *s) {
-  if (!s) return 0;
-  int rc = (int)hipEventRecord(s->joined, s->side);
-  if (!rc) rc = (int)hipStreamWaitEvent(st, s->joined, 0);
+static int join_side(Schedule &s) {
+  if (!s.open) return 0;
+  s.open = false;
+  int rc = (int)hipEventRecord(s.side->joined, s.side->side);
+  if (!rc) rc = (int)hipStreamWaitEvent(s.st, s.side->joined, 0);
   return rc;
 }
-// Two-chain step (the fused entry points at k_s <= 25, round 5): the forward's fork is NOT joined before the backward.
-// The dense-tile chain (forward, its rows' ssg_grad_rows pass, backward) and the direct chain (the same three for the
-// rows of the plan's sparse list) share nothing until the end: the row passes are per class anyway (split_backward), the
-// fixed-point scale of the deterministic accumulation comes from the a-priori bound of |G| (no maximum over all rows
-// to wait for), integer sums do not care who adds first, the criteria sums go to separate slots.  One join, then flush
-// and finalize.  Same bits as the joined schedule -- only the streams differ.  Against fork / join around forward and
-// backward each: one cross-stream round trip less, and the memory-bound row pass of one chain runs beside the VALU-bound
-// kernels of the other.
-// `gated`: the direct chain's backward is held (a one-way event: the dense chain never waits) until the dense chain's
-// row pass is through -- the schedule for steps whose long dense kernels dominate (two_chains_wanted() says no): the
-// direct backward then runs beside the dense backward and fills its tail instead of spending itself beside the dense
-// forward.  The loss finalize rides on the direct chain's stream behind the gate, off the critical path.
-struct ForkChain {
-  SideStream *fk = nullptr;
-  StreamPair sp{nullptr, nullptr};
-  bool active = false;   // forked by the forward, to be joined by the backward
-  bool gated = false;
-};
 
 // One 4-byte status word per device, owned by the library (allocated at the first call that can set it, never freed):
 // kernels that refuse their input without a host-visible error -- a dense kernel handed a plan cut for another tile
@@ -446,12 +420,6 @@ static bool tile_major_enabled() {
   return v != 0;
 }
 
-// Backward over a forward plan: G rows (+ criteria sums) by ssg_grad_rows, the dense tiles by the shared-term
-// kernel, the remaining rows by the direct kernel in GRAD_D mode.  `p` carries the sources as for launch_bwd.
-// the loss finalize of a GRAD_LOSS step: it needs ssg_grad_rows' partial sums only, so it is queued on the side stream
-// ahead of the direct backward kernel instead of at the very end of the caller's stream (7 us off the critical path)
-using FinalizeArgs = LossFinalize;   // {partials, nparts, n_dev, n_host, P, w_l1, w_kl, loss_out, nan_on_overflow}
-
 // nparts of a split backward's criteria sums: ssg_grad_rows' workgroups, then ssg_rows_tm's
 static int split_tm_tiles(const BwdParams &p, const TileMajor *tm) {
   if (!tm || tm->slots <= 0) return 0;
@@ -464,9 +432,13 @@ static bool split_row_classes(const BwdParams &p, int n_tm) {
   return p.mode == GRAD_LOSS && n_tm == 0 && p.row_scale && p.ks <= 25;
 }
 
-static int split_backward(BwdParams p, const int *rank, const int *plan, void *scratch, hipStream_t st,
-                          const FinalizeArgs *fin = nullptr, bool *fin_done = nullptr, const TileMajor *tm = nullptr,
-                          ForkChain *chain = nullptr) {
+// Backward over a forward plan: G rows (+ criteria sums) by ssg_grad_rows, the dense tiles by the shared-term
+// kernel, the remaining rows by the direct kernel in GRAD_D mode.  `p` carries the sources as for launch_bwd.  `fin`
+// (with `fin_done`): the loss finalize of a GRAD_LOSS step, launched here where the schedule has a place for it off
+// the critical path.  Joins the call's fork behind the backward kernels.
+static int split_backward(BwdParams p, const int *rank, const int *plan, void *scratch, Schedule &sc,
+                          const LossFinalize *fin = nullptr, bool *fin_done = nullptr, const TileMajor *tm = nullptr) {
+  const hipStream_t st = sc.st;
   float *G = (float *)scratch;
   const size_t nfl = align_up(sizeof(float) * (size_t)(p.n_host > 0 ? p.n_host : 1), 256);
   float *sum_b = (float *)((char *)scratch + align_up(sizeof(float) * (size_t)p.n_host * p.ks * p.ks, 256));
@@ -507,54 +479,34 @@ static int split_backward(BwdParams p, const int *rank, const int *plan, void *s
   const bool classes = split_row_classes(p, n_tm);
   // A backward on its own (ssg_loss_backward: the deferred loop's node, the module) forks HERE and runs the same two
   // chains from the row passes on: the sparse list's pass beside the dense-tile rows' instead of behind it.
-  ForkChain local;
-  // (the hint is written by the GPU asynchronously: ONE read per decision, or a flip between two reads could record a
-  // gated pair into a capturing stream)
-  const bool free_wanted = two_chains_wanted();
-  if (!(chain && chain->active) && classes && p.grad && !(dbg_mask() & ((1 << 27) | (1 << 28) | (1 << 29))) &&
-      two_chains_allowed() && (free_wanted || !stream_capturing(st))) {
-    SideStream *fk0 = nullptr;
-    hipStream_t st20 = fork_from(st, p.ks, fk0);
-    if (fk0 && st20 != st) {
-      local.fk = fk0;
-      local.sp = assign_streams(st, st20);
-      local.active = true;
-      local.gated = !free_wanted;
-      chain = &local;
-    }
-  }
-  const bool chained = chain && chain->active;
-  hipStream_t sd = chained ? chain->sp.dense : st, ss = chained ? chain->sp.direct : st;
-  auto leave = [&](int rc0) {   // (a forward that left its streams forked is joined on every way out)
-    if (!chained) return rc0;
-    const int rcj = join_to(st, chain->fk);
-    chain->active = false;
-    return rc0 ? rc0 : rcj;
-  };
-  if (chained && !(classes && p.grad)) return leave(SSG_E_BADARG);
+  if (sc.chains && !sc.open && classes && p.grad) fork_side(sc, dbg_mask() & ((1 << 27) | (1 << 28) | (1 << 29)));
+  // Gated chains: the direct backward is released once the dense FORWARD is through and runs beside the memory-bound
+  // dense row pass -- C2 1.1996 -> 1.178 ms against a release behind that row pass, three alternations
+  // (profiles/r6_schedule_ab.txt; holding the direct FORWARD until the dense forward is through as well: 1.184 alone,
+  // 1.20 together).  The loss finalize follows the direct backward on its stream, behind a second event for the dense
+  // chain's row pass.
+  const bool gated = sc.open && sc.gated;
   if (apriori) {
     g.gmax_part = nullptr;
     g.fix_word = (unsigned *)(p.gfix + n_fix);
   }
-  int rc = 0;
-  if (dbg_mask() & (1 << 29)) {
-  } else if (classes) {
-    const unsigned gg = grow_grid(p.n_host);
-    const bool early = chained && chain->gated && sd == st && ss != st && !(sched_mode() & 1);
-    if (early) rc = (int)hipEventRecord(chain->fk->gate, sd);   // (behind the dense forward, in front of its row pass)
-    GrowParams gd = g;   // the dense-tile rows
-    gd.only = 1;
-    if (!rc) rc = launch_grad_rows(gd, p.ks, p.kw, sd);
-    GrowParams gs = g;   // the plan's sparse list; its criteria sums behind the first pass's
-    gs.only = 2;
-    gs.grid_cap = 4096;
-    gs.tm_hdr = plan + 1;
-    gs.tm_slots = 0;
-    gs.sparse_order = plan + fwd_plan_order_offset(p.B, p.H, p.W);
-    gs.partials = p.partials + 2 * (size_t)gg;
-    if (!rc) rc = launch_grad_rows(gs, p.ks, p.kw, ss);
-  } else {
-    rc = launch_grad_rows(g, p.ks, p.kw, st);
+  int rc = gated ? (int)hipEventRecord(sc.side->gate, st) : 0;   // (behind the dense forward, in front of its row pass)
+  if (!rc && !(dbg_mask() & (1 << 29))) {
+    if (classes) {
+      GrowParams gd = g;   // the dense-tile rows
+      gd.only = 1;
+      rc = launch_grad_rows(gd, p.ks, p.kw, sc.dense());
+      GrowParams gs = g;   // the plan's sparse list; its criteria sums behind the first pass's
+      gs.only = 2;
+      gs.grid_cap = 4096;
+      gs.tm_hdr = plan + 1;
+      gs.tm_slots = 0;
+      gs.sparse_order = plan + fwd_plan_order_offset(p.B, p.H, p.W);
+      gs.partials = p.partials + 2 * (size_t)grow_grid(p.n_host);
+      if (!rc) rc = launch_grad_rows(gs, p.ks, p.kw, sc.direct());
+    } else {
+      rc = launch_grad_rows(g, p.ks, p.kw, st);
+    }
   }
   if (!rc && n_tm > 0) {   // the rows of the tile-major tiles (ssg_grad_rows skipped them: negative row scale)
     TmRowsParams t{};
@@ -586,10 +538,10 @@ static int split_backward(BwdParams p, const int *rank, const int *plan, void *s
     }
     rc = (dbg_mask() & (1 << 29)) ? 0 : launch_rows_tm(t, p.ks, p.kw, st);
   }
-  if (rc || !p.grad) return leave(rc);
+  if (rc || !p.grad) return rc;   // (two chains still forked: the entry point joins them)
   if (p.gfix && !apriori) {
     rc = launch_grad_fix_reduce(gmax_part, (int)grow_grid(p.n_host) + rows_tm_parts(n_tm), p.gfix, n_fix, st);
-    if (rc) return leave(rc);
+    if (rc) return rc;
   }
   const float *grows = p.mode == GRAD_D ? p.gin : G;
   DenseBwdParams d{};
@@ -621,55 +573,21 @@ static int split_backward(BwdParams p, const int *rank, const int *plan, void *s
     d.w_kl = p.w_kl;
     d.upstream = p.upstream;
   }
-  if (chained) {   // two-chain step: each backward kernel behind its own chain's row pass; then the one join
-    const bool early = chain->gated && sd == st && ss != st && !(sched_mode() & 1);
-    if (chain->gated && sd == st && ss != st && !early) {
-      rc = (int)hipEventRecord(chain->fk->gate, sd);
-      if (!rc) rc = (int)hipStreamWaitEvent(ss, chain->fk->gate, 0);
-      if (!rc && fin) {   // (both passes' criteria sums are complete behind the gate)
-        rc = launch_loss_finalize(fin->partials, fin->nparts, fin->n_dev, fin->n_host, fin->P, fin->w_l1, fin->w_kl,
-                                  fin->loss_out, fin->nan_on_overflow, ss, fin->set_size);
-        if (!rc && fin_done) *fin_done = true;
-      }
-      if (rc) return leave(rc);
-    }
-    if (early) {   // the direct backward waits for the dense FORWARD only; the finalize, behind it, for the dense row pass
-      rc = (int)hipStreamWaitEvent(ss, chain->fk->gate, 0);
-      if (!rc) rc = (int)hipEventRecord(chain->fk->gate2, sd);
-      if (rc) return leave(rc);
-    }
-    rc = launch_bwd_dense(d, p.ks, p.kw, p.C, sd);
-    if (!rc) {
-      BwdParams s = p;
-      s.mode = GRAD_D;
-      s.gin = grows;
-      s.order = plan + fwd_plan_order_offset(p.B, p.H, p.W);
-      s.n_dev = plan;  // n_sparse
-      s.partials = nullptr;
-      s.rows_hint = hint_sparse_rows();
-      rc = launch_bwd(s, ss);
-    }
-    if (!rc && early && fin) {
-      rc = (int)hipStreamWaitEvent(ss, chain->fk->gate2, 0);
-      if (!rc) rc = launch_loss_finalize(fin->partials, fin->nparts, fin->n_dev, fin->n_host, fin->P, fin->w_l1, fin->w_kl,
-                                         fin->loss_out, fin->nan_on_overflow, ss, fin->set_size);
-      if (!rc && fin_done) *fin_done = true;
-    }
-    return leave(rc);
+  if (gated) {   // the direct backward waits for the dense FORWARD only; the finalize, behind it, for the dense row pass
+    rc = (int)hipStreamWaitEvent(sc.direct(), sc.side->gate, 0);
+    if (!rc) rc = (int)hipEventRecord(sc.side->gate2, sc.dense());
   }
-  SideStream *fk = nullptr;
-  hipStream_t st2 = (dbg_mask() & ((1 << 27) | (1 << 28))) ? st : fork_from(st, p.ks, fk);
-  // (which kernel runs on which stream: ssg_set_overlap.  With a side stream the loss finalize -- it needs ssg_grad_rows'
-  // partial sums only -- is queued there ahead of that stream's kernel, off the critical path; on one stream it rides in
-  // the last workgroup of grad_fix_flush (det_end, round 5) or, without a fixed-point buffer, follows the backward.)
-  if (fin && fk && st2 != st) {
-    rc = launch_loss_finalize(fin->partials, fin->nparts, fin->n_dev, fin->n_host, fin->P, fin->w_l1, fin->w_kl,
-                              fin->loss_out, fin->nan_on_overflow, st2, fin->set_size);
-    if (rc) return rc;
-    if (fin_done) *fin_done = true;
+  if (!sc.open) {   // fork / join around this pass
+    fork_side(sc, dbg_mask() & ((1 << 27) | (1 << 28)));
+    // (with a side stream the loss finalize -- it needs ssg_grad_rows' partial sums only -- is queued there ahead of
+    // that stream's kernel, off the critical path (7 us); on one stream it rides in the last workgroup of
+    // grad_fix_flush (det_end, round 5) or, without a fixed-point buffer, follows the backward)
+    if (!rc && fin && sc.open) {
+      rc = launch_loss_finalize(*fin, sc.side->side);
+      if (!rc) *fin_done = true;
+    }
   }
-  const StreamPair sp = assign_streams(st, st2);
-  rc = (dbg_mask() & (1 << 27)) ? 0 : launch_bwd_dense(d, p.ks, p.kw, p.C, sp.dense);
+  if (!rc && !(dbg_mask() & (1 << 27))) rc = launch_bwd_dense(d, p.ks, p.kw, p.C, sc.dense());
   if (!rc && !(dbg_mask() & (1 << 28))) {
     BwdParams s = p;
     s.mode = GRAD_D;
@@ -677,11 +595,15 @@ static int split_backward(BwdParams p, const int *rank, const int *plan, void *s
     s.order = plan + fwd_plan_order_offset(p.B, p.H, p.W);
     s.n_dev = plan;  // n_sparse
     s.partials = nullptr;
-    s.rows_hint = hint_sparse_rows();
-    rc = launch_bwd(s, sp.direct);
+    s.rows_hint = sc.rows_hint;
+    rc = launch_bwd(s, sc.direct());
   }
-
-  const int rcj = join_to(st, fk);
+  if (!rc && gated && fin) {   // (both passes' criteria sums are complete behind gate2)
+    rc = (int)hipStreamWaitEvent(sc.direct(), sc.side->gate2, 0);
+    if (!rc) rc = launch_loss_finalize(*fin, sc.direct());
+    if (!rc) *fin_done = true;
+  }
+  const int rcj = join_side(sc);
   return rc ? rc : rcj;
 }
 
@@ -886,15 +808,14 @@ int ssg_compute_similarity(const float *image, const int *pos, float *out, int m
       d.raw = 1;
       d.dbg = (dbg_mask() >> 16) & 0xff;
       d.status = device_status_word();
-      SideStream *fk = nullptr;
-      hipStream_t st2 = fork_from(st, psize, fk);
-      const StreamPair sp = assign_streams(st, st2);
-      rc = launch_fwd_dense(d, psize, ksize, channel, sp.dense);
+      Schedule sc = schedule(st, psize, false);
+      fork_side(sc);
+      rc = launch_fwd_dense(d, psize, ksize, channel, sc.dense());
       FwdParams q = p;
       q.order = o.plan + fwd_plan_order_offset(1, height, width);
       q.n_dev = o.plan;   // n_sparse
-      if (!rc) rc = launch_fwd(q, sp.direct);
-      const int rcj = join_to(st, fk);
+      if (!rc) rc = launch_fwd(q, sc.direct());
+      const int rcj = join_side(sc);
       if (!rc) rc = rcj;
       q.order = o.dup;
       q.n_dev = o.ndup;
@@ -937,7 +858,8 @@ int ssg_compute_similarity_backward(const float *image, const float *grads, cons
     if (!rc && o.base) {
       // the split backward in GRAD_D mode (`grads` ARE the G rows): border sums by ssg_grad_rows, dense tiles by the
       // shared-term kernel, the plan's sparse rows by the direct one; then the duplicates of a position on their own
-      rc = split_backward(p, o.rank, o.plan, o.bscratch, st);
+      Schedule sc = schedule(st, psize, false);
+      rc = split_backward(p, o.rank, o.plan, o.bscratch, sc);
       BwdParams q = p;
       q.order = o.dup;
       q.n_dev = o.ndup;
@@ -984,8 +906,8 @@ int ssg_edge_mask_laplacian(const float *gt, int B, int H, int W, float lap_thre
 static int map_forward_impl(const float *img, const float *img2, int B, int C, int H, int W, const int *edges,
                             const int *tile_order, const int *rank_map, const int *fwd_plan, const int *n_edges_dev,
                             int n_rows, int ks, int kw, float sigma, float eps, int generalization, float *ssg,
-                            float *ssg2, double *row_scale, bool row_scale_zeroed, ssg_stream_t stream,
-                            const TileMajor *tm = nullptr, ForkChain *chain = nullptr) {
+                            float *ssg2, double *row_scale, bool row_scale_zeroed, Schedule &sc,
+                            const TileMajor *tm = nullptr) {
   if (n_rows < 0 || !sizes_ok(ks, kw) || B <= 0 || C <= 0) return SSG_E_BADARG;
   if (H <= ks / 2 || W <= ks / 2) return SSG_E_IMAGESMALL;
   if (n_rows == 0) return 0;
@@ -1043,36 +965,29 @@ static int map_forward_impl(const float *img, const float *img2, int B, int C, i
       d.strips = d.max_strips ? fwd_plan + fwd_plan_strip_offset(B, H, W) : nullptr;
     }
     if (row_scale && !row_scale_zeroed) {   // 0 = "this row is already normalised" (the rows of the direct kernels)
-      const int rc0 = (int)hipMemsetAsync(row_scale, 0, sizeof(double) * 2 * (size_t)n_rows, (hipStream_t)stream);
+      const int rc0 = (int)hipMemsetAsync(row_scale, 0, sizeof(double) * 2 * (size_t)n_rows, sc.st);
       if (rc0) return rc0;
     }
-    SideStream *fk = nullptr;
-    hipStream_t st = (hipStream_t)stream;
-    hipStream_t st2 = (dbg_mask() & ((1 << 25) | (1 << 26))) ? st : fork_from(st, ks, fk);
-    const StreamPair sp = assign_streams(st, st2);   // (ssg_set_overlap)
-    int rc = (dbg_mask() & (1 << 25)) ? 0 : launch_fwd_dense(d, ks, kw, C, sp.dense);
+    fork_side(sc, dbg_mask() & ((1 << 25) | (1 << 26)));   // (ssg_set_overlap)
+    int rc = (dbg_mask() & (1 << 25)) ? 0 : launch_fwd_dense(d, ks, kw, C, sc.dense());
     p.order = fwd_plan + fwd_plan_order_offset(B, H, W);
     p.n_dev = fwd_plan;  // n_sparse
-    p.rows_hint = hint_sparse_rows();
-    if (!rc && !(dbg_mask() & (1 << 26))) rc = launch_fwd(p, sp.direct);
-    if (!rc && chain && fk && st2 != st) {   // two-chain step: the backward's kernels follow on the same two streams
-      chain->fk = fk;
-      chain->sp = sp;
-      chain->active = true;
-      return 0;
-    }
-    const int rcj = join_to(st, fk);
+    p.rows_hint = sc.rows_hint;
+    if (!rc && !(dbg_mask() & (1 << 26))) rc = launch_fwd(p, sc.direct());
+    if (sc.chains) return rc;   // two chains: the backward's kernels follow on the same two streams (the caller joins)
+    const int rcj = join_side(sc);
     return rc ? rc : rcj;
   }
-  return launch_fwd(p, (hipStream_t)stream);
+  return launch_fwd(p, sc.st);
 }
 
 int ssg_map_forward(const float *img, const float *img2, int B, int C, int H, int W, const int *edges,
                     const int *tile_order, const int *rank_map, const int *fwd_plan, const int *n_edges_dev, int n_rows,
                     int ks, int kw, float sigma, float eps, int generalization, float *ssg, float *ssg2,
                     double *row_scale, ssg_stream_t stream) {
+  Schedule sc = schedule((hipStream_t)stream, ks, false);
   return map_forward_impl(img, img2, B, C, H, W, edges, tile_order, rank_map, fwd_plan, n_edges_dev, n_rows, ks, kw,
-                          sigma, eps, generalization, ssg, ssg2, row_scale, false, stream);
+                          sigma, eps, generalization, ssg, ssg2, row_scale, false, sc);
 }
 
 size_t ssg_backward_scratch_bytes(int n_rows, int ks) { return split_scratch_bytes(n_rows, ks); }
@@ -1108,7 +1023,8 @@ int ssg_map_backward(const float *img, int B, int C, int H, int W, const int *ed
   int rc = det_begin(p, grad_fix, (hipStream_t)stream);
   if (rc) return rc;
   if (split_ok(ks, kw, C, rank_map, fwd_plan, scratch)) {
-    rc = split_backward(p, rank_map, fwd_plan, scratch, (hipStream_t)stream);
+    Schedule sc = schedule((hipStream_t)stream, ks, false);
+    rc = split_backward(p, rank_map, fwd_plan, scratch, sc);
   } else {
     if (p.gfix) rc = launch_grad_fix_bound(p, (hipStream_t)stream);
     if (!rc) rc = launch_bwd(p, (hipStream_t)stream);
@@ -1131,22 +1047,12 @@ static int loss_backward(const float *sr, int B, int C, int H, int W, const int 
                          float sigma, int generalization, float *ssg_sr, float *ssg_gt, float w_l1, float w_kl,
                          const float *upstream, float *loss_out, float *grad_sr, void *scratch, void *grad_fix,
                          const double *row_scale, bool rows_scratch, bool fix_zeroed, bool grad_is_output,
-                         ssg_stream_t stream, const TileMajor *tm = nullptr, bool nan_on_overflow = false,
-                         ForkChain *chain = nullptr) {
+                         Schedule &sc, const TileMajor *tm = nullptr, bool nan_on_overflow = false) {
   if (n_rows < 0 || !sizes_ok(ks, kw) || B <= 0 || C <= 0 || !loss_out) return SSG_E_BADARG;
   if (H <= ks / 2 || W <= ks / 2) return SSG_E_IMAGESMALL;
-  hipStream_t st = (hipStream_t)stream;
-  // (a forward that left its streams forked is joined on every way out)
-  auto leave = [&](int rc0) {
-    if (chain && chain->active) {
-      const int rcj = join_to(st, chain->fk);
-      chain->active = false;
-      return rc0 ? rc0 : rcj;
-    }
-    return rc0;
-  };
-  if (n_rows == 0) return leave((int)hipMemsetAsync(loss_out, 0, 2 * sizeof(float), st));
-  if (!sr || !edges || !ssg_sr || !ssg_gt || !scratch) return leave(SSG_E_BADARG);
+  const hipStream_t st = sc.st;
+  if (n_rows == 0) return (int)hipMemsetAsync(loss_out, 0, 2 * sizeof(float), st);
+  if (!sr || !edges || !ssg_sr || !ssg_gt || !scratch) return SSG_E_BADARG;
   BwdParams p{};
   p.img = sr;
   p.grad = grad_sr;
@@ -1173,35 +1079,32 @@ static int loss_backward(const float *sr, int B, int C, int H, int W, const int 
   p.dbg = (dbg_mask() >> 8) & 0xff;
   p.row_scale = row_scale;
   p.rows_scratch = rows_scratch ? 1 : 0;
-  if (row_scale && !split_ok(ks, kw, C, rank_map, fwd_plan, scratch)) return leave(SSG_E_BADARG);  // only ssg_grad_rows rescales
-  int rc = det_begin(p, grad_fix, st, fix_zeroed);
-  if (rc) return leave(rc);
-  int nparts;
-  bool fin_done = false;
   const bool split = split_ok(ks, kw, C, rank_map, fwd_plan, scratch);
-  // (per-class row passes: two sets of grow_grid(n_rows) slots of criteria sums)
-  nparts = split ? (split_row_classes(p, split_tm_tiles(p, tm)) ? 2 : 1) * (int)grow_grid(n_rows) + rows_tm_parts(split_tm_tiles(p, tm)) : 0;
+  if (row_scale && !split) return SSG_E_BADARG;  // only ssg_grad_rows rescales
+  int rc = det_begin(p, grad_fix, st, fix_zeroed);
+  if (rc) return rc;
+  // criteria sums: the backward kernel's workgroups, or ssg_grad_rows' -- per-class row passes: two sets of
+  // grow_grid(n_rows) slots -- and ssg_rows_tm's
   // (ssg_grad_rows' slots come in sets of grow_grid(n_rows), live up to the device's row count: LossFinalize::set_size)
-  const int set_size = split && split_tm_tiles(p, tm) == 0 ? (int)grow_grid(n_rows) : 0;
+  const int n_tm = split ? split_tm_tiles(p, tm) : 0;
+  const int nparts = !split ? (int)bwd_grid(p)
+                            : (split_row_classes(p, n_tm) ? 2 : 1) * (int)grow_grid(n_rows) + rows_tm_parts(n_tm);
+  const int set_size = split && n_tm == 0 ? (int)grow_grid(n_rows) : 0;
+  const LossFinalize fin{p.partials, nparts, n_edges_dev, n_rows, ks * ks, w_l1, w_kl, loss_out, nan_on_overflow ? 1 : 0, set_size};
+  bool fin_done = false;
   if (split) {
-    const FinalizeArgs fin{p.partials, nparts, n_edges_dev, n_rows, ks * ks, w_l1, w_kl, loss_out, nan_on_overflow ? 1 : 0, set_size};
-    rc = split_backward(p, rank_map, fwd_plan, (char *)scratch + partials_bytes(B, H, W, n_rows), st, &fin, &fin_done, tm,
-                        chain);
+    rc = split_backward(p, rank_map, fwd_plan, (char *)scratch + partials_bytes(B, H, W, n_rows), sc, &fin, &fin_done, tm);
   } else {
-    rc = leave(0);
     p.fix_inline = p.gfix ? 1 : 0;   // (GRAD_LOSS: the backward kernel derives the a-priori scale itself -- one launch less)
-    if (!rc) rc = launch_bwd(p, st);
-    nparts = (int)bwd_grid(p);
+    rc = launch_bwd(p, st);
   }
-  const FinalizeArgs fin{p.partials, nparts, n_edges_dev, n_rows, ks * ks, w_l1, w_kl, loss_out, nan_on_overflow ? 1 : 0, set_size};
   // (the finalize rides in the flush's last workgroup when its partial sums are few -- 256 threads play its 1,024 lanes: C5's
   // 70 k partials took 30 us there against 10 + 11 as two launches)
   // (sets of slots are read up to the device's row count only: what counts is their live prefix, bounded by the host's)
   const int fin_reads = set_size > 0 ? (nparts / set_size) * ((n_rows + 3) / 4) : nparts;
   if (!rc) rc = det_end(p, st, grad_is_output, (fin_done || fin_reads > 8192) ? nullptr : &fin, &fin_done);
   if (rc || fin_done) return rc;
-  return launch_loss_finalize(p.partials, nparts, n_edges_dev, n_rows, ks * ks, w_l1, w_kl, loss_out, nan_on_overflow ? 1 : 0, st,
-                              set_size);
+  return launch_loss_finalize(fin, st);
 }
 
 int ssg_loss_backward(const float *sr, int B, int C, int H, int W, const int *edges, const int *tile_order,
@@ -1210,9 +1113,12 @@ int ssg_loss_backward(const float *sr, int B, int C, int H, int W, const int *ed
                       float *ssg_sr, float *ssg_gt, float w_l1, float w_kl, const float *upstream,
                       float *loss_out, float *grad_sr, void *scratch, void *grad_fix, const double *row_scale,
                       int rows_are_scratch, ssg_stream_t stream) {
-  return loss_backward(sr, B, C, H, W, edges, tile_order, rank_map, fwd_plan, n_edges_dev, n_rows, ks, kw, sigma,
-                       generalization, ssg_sr, ssg_gt, w_l1, w_kl, upstream, loss_out, grad_sr, scratch, grad_fix,
-                       row_scale, rows_are_scratch != 0, false, false, stream);
+  Schedule sc = schedule((hipStream_t)stream, ks, true);
+  const int rc = loss_backward(sr, B, C, H, W, edges, tile_order, rank_map, fwd_plan, n_edges_dev, n_rows, ks, kw, sigma,
+                               generalization, ssg_sr, ssg_gt, w_l1, w_kl, upstream, loss_out, grad_sr, scratch,
+                               grad_fix, row_scale, rows_are_scratch != 0, false, false, sc);
+  const int rcj = join_side(sc);   // (an error between the row passes' fork and the backward's join leaves it open)
+  return rc ? rc : rcj;
 }
 
 // two row-major regions (sr, gt); at k_s = 49 two tile-major regions of the same size behind them
@@ -1373,12 +1279,9 @@ static int loss_fwd_bwd_impl(const float *sr, const float *gt, const void *mask,
   // the row scales and the fixed-point gradient sums start at zero: cleared by the edge-list builder's first kernel
   // (16-byte granules: both sizes are multiples of 16)
   const bool zero_fix = grad_fix && grad_sr;
-  // two chains (ForkChain): sizes with a dense / direct split and a side stream to put one of them on
-  // (under capture only the free-running chains: a GATED pair replays badly, see stream_capturing)
-  const bool free_wanted = two_chains_wanted();   // (one read of the asynchronously written hint per decision)
-  const bool two_chains = defer && grad_sr && ks <= 25 && overlap_enabled() && two_chains_allowed() &&
-                          (free_wanted || !stream_capturing((hipStream_t)stream));
-  const bool free_running = two_chains && free_wanted;
+  // the schedule of the whole step, from the hint the builder below has not overwritten yet: two chains where there is a
+  // gradient and the sizes have a dense / direct split
+  Schedule sc = schedule((hipStream_t)stream, ks, defer && grad_sr);
   const size_t fix_bytes = sizeof(long long) * ((size_t)B * C * H * W + 8), rs_bytes = 2 * sizeof(double) * (size_t)capacity;
   int rc = edge_list_impl(mask_kind == 2 ? (const void *)gt : mask, mask_kind, mask_kind == 2 ? 3 : mask_channels, B, H,
                           W, mask_stride, lap_threshold, ks, edges, capacity, counts, rank, order, plan, escratch,
@@ -1391,16 +1294,14 @@ static int loss_fwd_bwd_impl(const float *sr, const float *gt, const void *mask,
     rc = (int)hipMemsetAsync((char *)grad_sr + ((sizeof(float) * (size_t)B * C * H * W) & ~(size_t)15), 0,
                              (sizeof(float) * (size_t)B * C * H * W) & 15, (hipStream_t)stream);
   if (rc) return rc;
-  ForkChain chain;
-  chain.gated = !free_running;
   rc = map_forward_impl(sr, gt, B, C, H, W, edges, order, rank, plan, counts, capacity, ks, kw, sigma, eps,
-                        generalization, ssg_sr, ssg_gt, defer ? row_scale : nullptr, defer, stream, &tm,
-                        two_chains ? &chain : nullptr);
-  if (rc) return rc;
-  return loss_backward(sr, B, C, H, W, edges, order, rank, plan, counts, capacity, ks, kw, sigma, generalization,
+                        generalization, ssg_sr, ssg_gt, defer ? row_scale : nullptr, defer, sc, &tm);
+  if (!rc)
+    rc = loss_backward(sr, B, C, H, W, edges, order, rank, plan, counts, capacity, ks, kw, sigma, generalization,
                        ssg_sr, ssg_gt, w_l1, w_kl, nullptr, loss_out, grad_sr, lscratch, grad_fix,
-                       defer ? row_scale : nullptr, fused, zero_fix, grad_is_output && zero_fix, stream, &tm, true,
-                       two_chains ? &chain : nullptr);
+                       defer ? row_scale : nullptr, fused, zero_fix, grad_is_output && zero_fix, sc, &tm, true);
+  const int rcj = join_side(sc);   // (an error between the forward's fork and the backward's join leaves it open)
+  return rc ? rc : rcj;
 }
 
 int ssg_loss_fwd_bwd(const float *sr, const float *gt, const void *mask, int mask_kind, int mask_channels, int B,

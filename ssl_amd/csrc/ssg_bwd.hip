@@ -924,10 +924,8 @@ int launch_bwd(const BwdParams &p, hipStream_t st) {
   return (int)hipGetLastError();
 }
 
-int launch_loss_finalize(const float *partials, int nparts, const int *n_dev, int n_host, int P, float w_l1,
-                         float w_kl, float *loss_out, int nan_on_overflow, hipStream_t st, int set_size) {
-  hipLaunchKernelGGL(ssg_loss_finalize, dim3(1), dim3(1024), 0, st,
-                     LossFinalize{partials, nparts, n_dev, n_host, P, w_l1, w_kl, loss_out, nan_on_overflow, set_size});
+int launch_loss_finalize(const LossFinalize &f, hipStream_t st) {
+  hipLaunchKernelGGL(ssg_loss_finalize, dim3(1), dim3(1024), 0, st, f);
   return (int)hipGetLastError();
 }
 

@@ -659,11 +659,36 @@ def test_loss_step_hip_graph_replay_matches_eager(dev):
     the losses/SSGs (gradient: fp32 atomics, order-dependent) -- also after the input CONTENT changes at
     the recorded addresses (different edge count: nothing host-side is baked into the recording) and after
     a call with other tensors (re-record)."""
-    from ssl_amd import engine, synth
-    B, H, W, ks, kw, sigma = 2, 80, 96, 25, 9, 0.004
+    from ssl_amd import synth
+    B, H, W = 2, 80, 96
+    _graph_replay_matches_eager(dev, B, H, W, lambda seed: synth.make_batch(B, H, W, seed0=seed))
+
+
+def test_loss_step_hip_graph_replay_matches_eager_gated(dev):
+    """The same with more than 512 dense tiles whose rows carry the step: the eager step runs the GATED chains, which a
+    capture does not take -- the recorded step forks and joins around each pass instead (ssg_api.hip, schedule())."""
+    from ssl_amd import synth
+    B, H, W = 2, 256, 320
+
+    def make(seed):
+        sr, gt, _ = synth.make_batch(B, H, W, seed0=seed)
+        mask = (np.random.default_rng(seed).random((B, 1, H, W)) < 0.25).astype(np.float32)
+        # the plan's census: 8 x 32 tiles, dense from 16 edge pixels (the default threshold); the rest left to the
+        # direct kernels, whose 38 ns a row against 0.74 us a dense tile decide which chain is the longer one
+        px = mask.reshape(B, H // 8, 8, W // 32, 32).sum(axis=(2, 4))
+        n_tiles, n_sparse = int((px >= 16).sum()), int(px[px < 16].sum())
+        assert n_tiles > 512 and n_sparse * 38 <= n_tiles * 740
+        return sr, gt, mask
+
+    _graph_replay_matches_eager(dev, B, H, W, make)
+
+
+def _graph_replay_matches_eager(dev, B, H, W, make):
+    from ssl_amd import engine
+    ks, kw, sigma = 25, 9, 0.004
     eager = engine.LossStep(B, 3, H, W, ks, kw, sigma, 1e-10, True, 1e3, 1e3, device=dev)
     graph = engine.LossStep(B, 3, H, W, ks, kw, sigma, 1e-10, True, 1e3, 1e3, device=dev, graph=True)
-    sr_np, gt_np, m_np = synth.make_batch(B, H, W, seed0=900)
+    sr_np, gt_np, m_np = make(900)
     sr, gt, mask = T(sr_np, dev), T(gt_np, dev), T(m_np, dev)
 
     def same():
@@ -679,7 +704,7 @@ def test_loss_step_hip_graph_replay_matches_eager(dev):
     n1 = same()
     n1b = same()                                   # replay
     assert n1 == n1b and graph._graph is not None
-    sr2, gt2, m2 = synth.make_batch(B, H, W, seed0=950)
+    sr2, gt2, m2 = make(950)
     sr.copy_(T(sr2, dev)); gt.copy_(T(gt2, dev)); mask.copy_(T(m2, dev))   # new content, same addresses
     n2 = same()
     assert n2 != n1
@@ -885,7 +910,7 @@ def test_stream_assignment_follows_the_last_plan(dev):
             loss2, grad2 = step2(T(sr_np, dev), T(gt_np, dev), T(mask, dev))
             assert L.ssg_last_overlap_assignment() == 3 - want
             # bit for bit: integer accumulation at a scale that does not depend on the schedule, criteria sums grouped
-            # per row class on one stream and on two (mode 3 may also run the two chains unjoined: ssg_api.hip, ForkChain)
+            # per row class on one stream and on two (mode 3 may also run the two chains unjoined: ssg_api.hip, Schedule)
             assert torch.equal(loss, loss2) and torch.equal(grad, grad2)
             engine.set_overlap(3)
     finally:
