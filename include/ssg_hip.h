@@ -61,6 +61,8 @@ typedef void *ssg_stream_t; /* hipStream_t */
  * the product library no longer reads ANY environment variable (SSG_DENSE_THR, SSG_OVERLAP, SSG_OP_PLAN_FROM ... are
  * honoured by the profiling build only); the one-wave tile-major dense backward is gone. */
 /* 6 (round 6): + ssg_set_tiny_step; default dense threshold 16. */
+/* 6, additive: + ssg_ldl_workspace_bytes, ssg_artifact_map, ssg_artifact_map_backward, ssg_ldl_loss, ssg_local_variance
+ * (LDL's artifact map, section (F)); nothing existing changed, so the version number stays. */
 int ssg_abi_version(void);
 const char *ssg_status_string(int status);
 /* Device-side refusals that no return value can carry (everything is asynchronous): waits for `stream`, then returns
@@ -456,6 +458,39 @@ int ssg_poisson_rates(const float *img, float *rate_color, float *rate_gray, flo
 int ssg_poisson_noise(const float *img, float *out, const float *draw_color, const float *draw_gray, const float *vals,
                       const float *scale, const float *gray, int B, int C, int H, int W, int clip, int rounds,
                       ssg_stream_t stream);
+
+/* ---------------------------------------------------------------- (F) ----
+ * LDL's artifact map and loss (basicsr/losses/loss_util.py:106-161; callers ldlssl_model.py:220-224 and
+ * realesrgan_model.py:222-226: pixel_weight = get_refined_artifact_map(gt, output, output_ema, 7), then
+ * L1Loss(pixel_weight * output, pixel_weight * gt)), ssl_amd/csrc/ssg_ldl.hip.  output, gt, ema (B,C,H,W) fp32:
+ *   r = sum_c |gt - output|, r_e = sum_c |gt - ema|, P_b = var_unbiased(r_b)^(1/5),
+ *   V_p = unbiased variance of the k x k reflect-padded window of r around p,
+ *   w = P_b V_p, set to 0 where r < r_e (ema non-null: get_refined_artifact_map; ema NULL: get_artifact_map).
+ * k odd, 3 <= k <= 15 (7 is the compiled fast path); any C >= 1; H, W > (k-1)/2.  Status: SSG_E_BADARG for a null
+ * pointer, k even or < 3, B, C, H or W <= 0; SSG_E_TOOLARGE for k > 15; SSG_E_IMAGESMALL for H or W <= (k-1)/2 (torch's
+ * reflect pad raises); SSG_E_WORKSPACE for workspace_bytes < ssg_ldl_workspace_bytes(B, H, W); SSG_E_ALIGN for a
+ * workspace that is not 16-byte aligned.  Three launches at
+ * most, no atomics, fixed summation orders: results are bit-reproducible.  The gradient is with respect to `output`
+ * only.  An image whose residual r is constant (output == gt) has var = 0; like the reference's pow backward (0 * inf)
+ * its whole gradient is NaN.
+ * ssg_artifact_map: w_out (B,1,H,W).
+ * ssg_artifact_map_backward: grad_output (B,C,H,W) = d/d output of sum(grad_w * w) (overwritten).
+ * ssg_ldl_loss: loss_out[0] = loss_weight * mean |w*output - w*gt| (mean != 0; the sum otherwise), the products rounded
+ *   separately in fp32; grad_output (nullable) = d loss / d output (overwritten).
+ * ssg_local_variance (get_local_weights): residual (B,1,H,W) planes taken as they are (no abs, no P, no mask):
+ *   v_out (nullable) = V; with grad_v and grad_residual (both or neither) grad_residual = d/d residual of sum(grad_v V). */
+size_t ssg_ldl_workspace_bytes(int B, int H, int W);
+int ssg_artifact_map(const float *output, const float *gt, const float *ema /* nullable */, int B, int C, int H, int W,
+                     int k, float *w_out, void *workspace, size_t workspace_bytes, ssg_stream_t stream);
+int ssg_artifact_map_backward(const float *output, const float *gt, const float *ema /* nullable */,
+                              const float *grad_w, int B, int C, int H, int W, int k, float *grad_output,
+                              void *workspace, size_t workspace_bytes, ssg_stream_t stream);
+int ssg_ldl_loss(const float *output, const float *gt, const float *ema /* nullable */, int B, int C, int H, int W,
+                 int k, float loss_weight, int mean, float *loss_out, float *grad_output /* nullable */,
+                 void *workspace, size_t workspace_bytes, ssg_stream_t stream);
+int ssg_local_variance(const float *residual, int B, int H, int W, int k, float *v_out /* nullable */,
+                       const float *grad_v /* nullable */, float *grad_residual /* nullable */, void *workspace,
+                       size_t workspace_bytes, ssg_stream_t stream);
 
 #ifdef SSG_PROFILE
 /* PROFILING BUILD ONLY (libssg_hip_prof.so, compiled with -DSSG_PROFILE; the product library libssg_hip.so does not

@@ -452,3 +452,135 @@ class LossStep:
             self._graph, self._graph_key, self._graph_refs = g, key, (sr, gt, mp)   # keep the recorded buffers alive
         self._graph.replay()
         return self.loss, self.grad
+
+
+# ------------------------------------------------------------------------- LDL's artifact map (ssg_ldl.hip) ----
+def _ldl_prepare(output, gt, ema, ksize):
+    """fp32 contiguous copies of (output, gt, ema) after the checks every LDL entry point makes."""
+    _need_gpu(output, gt, ema)
+    for name, t in (("gt", gt), ("ema", ema)):
+        if t is not None and t.requires_grad:
+            raise ValueError(f"ssl_amd: LDL's artifact map is differentiable with respect to the output only, but `{name}` "
+                             "requires grad; detach it (both reference callers pass it without a gradient)")
+    if output.dim() != 4 or gt.shape != output.shape or (ema is not None and ema.shape != output.shape):
+        raise ValueError(f"ssl_amd: output, gt (and ema) must be (B,C,H,W) of one shape, got {tuple(output.shape)}, "
+                         f"{tuple(gt.shape)}" + ("" if ema is None else f", {tuple(ema.shape)}"))
+    return _f32c(output), _f32c(gt), None if ema is None else _f32c(ema), int(ksize)
+
+
+def _ldl_workspace(B, H, W, dev):
+    n = _lib.lib().ssg_ldl_workspace_bytes(B, H, W)
+    return torch.empty(max(n, 1), dtype=torch.uint8, device=dev), n
+
+
+class _ArtifactMapFn(torch.autograd.Function):
+    """w = get_(refined_)artifact_map(gt, output, ema, k) (loss_util.py:129-161), (B,1,H,W); backward: one
+    ssg_artifact_map_backward call for any upstream dL/dw."""
+
+    @staticmethod
+    def forward(ctx, output, gt, ema, k):
+        x, y, z, k = _ldl_prepare(output, gt, ema, k)
+        B, C, H, W = x.shape
+        w = torch.empty((B, 1, H, W), dtype=torch.float32, device=x.device)
+        ws, nb = _ldl_workspace(B, H, W, x.device)
+        with torch.cuda.device(x.device):
+            _lib.check(_lib.lib().ssg_artifact_map(_ptr(x), _ptr(y), _ptr(z), B, C, H, W, k, _ptr(w), _ptr(ws), nb,
+                                                   _stream()))
+        if ctx.needs_input_grad[0]:
+            ctx.save_for_backward(x, y, z)
+        ctx.k, ctx.in_dtype = k, output.dtype
+        return w.to(output.dtype)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_w):
+        x, y, z = ctx.saved_tensors
+        B, C, H, W = x.shape
+        gw = _f32c(grad_w)
+        grad = torch.empty_like(x)
+        ws, nb = _ldl_workspace(B, H, W, x.device)
+        with torch.cuda.device(x.device):
+            _lib.check(_lib.lib().ssg_artifact_map_backward(_ptr(x), _ptr(y), _ptr(z), _ptr(gw), B, C, H, W, ctx.k,
+                                                            _ptr(grad), _ptr(ws), nb, _stream()))
+        return grad.to(ctx.in_dtype), None, None, None
+
+
+def artifact_map(output, gt, ema=None, ksize=7):
+    """LDL's artifact map (B,1,H,W) of a batch, differentiable with respect to `output`: get_refined_artifact_map with
+    `ema`, get_artifact_map without.  fp16 / bf16 inputs are computed in fp32.  An image whose residual is constant
+    (output == gt) gets a NaN gradient, as in the reference (its pow backward forms 0 * inf)."""
+    return _ArtifactMapFn.apply(output, gt, ema, ksize)
+
+
+class _LdlLossFn(torch.autograd.Function):
+    """loss_weight * mean (or sum) |w*output - w*gt| with w = artifact_map(output, gt, ema): ONE ssg_ldl_loss call
+    produces the loss and d loss / d output together (the gradient through the map included); backward() only scales
+    that gradient by the incoming one (the pattern of _SSGLossFn)."""
+
+    @staticmethod
+    def forward(ctx, output, gt, ema, k, loss_weight, mean):
+        x, y, z, k = _ldl_prepare(output, gt, ema, k)
+        B, C, H, W = x.shape
+        loss = torch.empty(1, dtype=torch.float32, device=x.device)
+        grad = torch.empty_like(x) if ctx.needs_input_grad[0] else None
+        ws, nb = _ldl_workspace(B, H, W, x.device)
+        with torch.cuda.device(x.device):
+            _lib.check(_lib.lib().ssg_ldl_loss(_ptr(x), _ptr(y), _ptr(z), B, C, H, W, k, float(loss_weight),
+                                               int(bool(mean)), _ptr(loss), _ptr(grad), _ptr(ws), nb, _stream()))
+        if grad is not None:
+            ctx.save_for_backward(grad)
+        ctx.in_dtype = output.dtype
+        return loss[0]
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        grad, = ctx.saved_tensors
+        return (grad * g.to(torch.float32).reshape(())).to(ctx.in_dtype), None, None, None, None, None
+
+
+def ldl_loss(output, gt, ema=None, ksize=7, loss_weight=1.0, reduction='mean'):
+    """L1Loss(w * output, w * gt) with w = artifact_map(output, gt, ema, ksize), fused: the callers'
+    ldlssl_model.py:220-224 / realesrgan_model.py:222-226 in one call.  reduction 'mean' or 'sum'."""
+    if reduction not in ('mean', 'sum'):
+        raise ValueError(f"ssl_amd: ldl_loss fuses the 'mean' and 'sum' reductions only, got {reduction!r}")
+    return _LdlLossFn.apply(output, gt, ema, ksize, loss_weight, reduction == 'mean')
+
+
+class _LocalVarFn(torch.autograd.Function):
+    """get_local_weights (loss_util.py:106-126): unbiased variance of the k x k reflect-padded window, per plane."""
+
+    @staticmethod
+    def forward(ctx, residual, k):
+        _need_gpu(residual)
+        if residual.dim() != 4:
+            raise ValueError(f"ssl_amd: get_local_weights takes a (B,C,H,W) residual, got {tuple(residual.shape)}")
+        r = _f32c(residual)
+        B, C, H, W = r.shape
+        v = torch.empty_like(r)
+        ws, nb = _ldl_workspace(B * C, H, W, r.device)
+        with torch.cuda.device(r.device):
+            _lib.check(_lib.lib().ssg_local_variance(_ptr(r), B * C, H, W, int(k), _ptr(v), None, None, _ptr(ws), nb,
+                                                     _stream()))
+        if ctx.needs_input_grad[0]:
+            ctx.save_for_backward(r)
+        ctx.k, ctx.in_dtype = int(k), residual.dtype
+        return v.to(residual.dtype)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_v):
+        r, = ctx.saved_tensors
+        B, C, H, W = r.shape
+        gv = _f32c(grad_v)
+        grad = torch.empty_like(r)
+        ws, nb = _ldl_workspace(B * C, H, W, r.device)
+        with torch.cuda.device(r.device):
+            _lib.check(_lib.lib().ssg_local_variance(_ptr(r), B * C, H, W, ctx.k, None, _ptr(gv), _ptr(grad), _ptr(ws),
+                                                     nb, _stream()))
+        return grad.to(ctx.in_dtype), None
+
+
+def local_variance(residual, ksize):
+    """get_local_weights(residual, ksize): (B,C,H,W) -> (B,C,H,W), differentiable with respect to `residual`."""
+    return _LocalVarFn.apply(residual, ksize)

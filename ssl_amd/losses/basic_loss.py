@@ -287,3 +287,26 @@ class SSGLoss(nn.Module):
             self._pending.append((ev, host, cap, sr.device.index))
         self.last_counts = counts
         return out
+
+
+class ArtifactLoss(nn.Module):
+    """LDL's artifact loss as its callers write it (ldlssl_model.py:220-224, realesrgan_model.py:222-226):
+    forward(output, gt, output_ema=None) == L1Loss(loss_weight, reduction)(w * output, w * gt) with
+    w = get_refined_artifact_map(gt, output, output_ema, ksize) (get_artifact_map when output_ema is None).
+    'mean' and 'sum' run one fused call (ssg_ldl_loss: the map, the loss and the gradient through both); 'none' composes
+    the differentiable map with the element-wise L1.  Gradient with respect to `output` only; an image whose output
+    equals its GT gets a NaN gradient, as in the reference."""
+
+    def __init__(self, loss_weight=1.0, ksize=7, reduction='mean'):
+        super(ArtifactLoss, self).__init__()
+        if reduction not in _reduction_modes:
+            raise ValueError(f'Unsupported reduction mode: {reduction}. Supported ones are: {_reduction_modes}')
+        self.loss_weight = loss_weight
+        self.ksize = ksize
+        self.reduction = reduction
+
+    def forward(self, output, gt, output_ema=None):
+        if self.reduction in ('mean', 'sum'):
+            return engine.ldl_loss(output, gt, output_ema, self.ksize, self.loss_weight, self.reduction)
+        w = engine.artifact_map(output, gt, output_ema, self.ksize)
+        return self.loss_weight * F.l1_loss(w * output, w * gt, reduction='none')

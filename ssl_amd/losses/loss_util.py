@@ -69,6 +69,30 @@ def eager_rows(img, mask, conv, kernel_size_search, kernel_size_window, sigma, e
     return s.unsqueeze(0)           # 1, num, k_s*k_s
 
 
+def get_local_weights(residual, ksize):
+    """LDL's local weights (loss_util.py:106-126): the unbiased variance of the ksize x ksize window of `residual`
+    (B,C,H,W), reflect-padded by (ksize-1)/2, per channel.  Differentiable with respect to `residual`.  GPU only;
+    ksize odd, 3..15 (ssg_local_variance)."""
+    engine._need_gpu(residual)
+    return engine.local_variance(residual, ksize)
+
+
+def get_artifact_map(img_gt, img_output, ksize):
+    """LDL's artifact map without the EMA refinement (loss_util.py:129-137): var(r)^(1/5) * get_local_weights(r) with
+    r = sum_c |img_gt - img_output|, (B,1,H,W).  Differentiable with respect to `img_output` (only: `img_gt` must not
+    require grad).  An image whose residual is constant (img_output == img_gt) gets a NaN gradient, exactly as the
+    reference's `** (1/5)` backward gives it (0 * inf).  GPU only (ssg_artifact_map)."""
+    return engine.artifact_map(img_output, img_gt, None, ksize)
+
+
+def get_refined_artifact_map(img_gt, img_output, img_ema, ksize):
+    """LDL's artifact map (loss_util.py:140-161): get_artifact_map's weight, set to 0 where the output's residual is
+    strictly below the EMA model's.  Differentiable with respect to `img_output` only (`img_gt` / `img_ema` must not
+    require grad; the reference callers pass them detached).  Constant residual: NaN gradient for that image, as in
+    the reference.  GPU only (ssg_artifact_map)."""
+    return engine.artifact_map(img_output, img_gt, img_ema, ksize)
+
+
 class similarity_map():
     def __init__(self, img, mask=None, ssl_mode='cuda', kernel_size_search=5, generalization=True,
                  kernel_size_window=9, sigma=0.004, eps=1e-10):
