@@ -111,9 +111,51 @@ def test_restatement_matches_the_reference_fixture(golden):
     assert saw_nan      # the constant-residual image is in the fixture and its gradient is NaN in the reference
 
 
+def test_reference64_matches_the_reference_fixture(golden):
+    """The fp64 yardstick of the GPU tests (ldl_reference.py) against the same outputs of the reference, to the same
+    1e-6 and NaN pattern as the fp32 restatement above; its fp32-decided residual and mask equal the reference's
+    bit for bit."""
+    from ldl_reference import local_variance64, mask32, reference64, residual32
+    f = golden("f18_ldl_artifact")
+    saw_nan = False
+    for i in range(int(f["n_cases"])):
+        c = lambda key: f[f"c{i}_{key}"]
+        o, g, e = (torch.from_numpy(c(key)) for key in ("o", "g", "e"))
+        k, lam = int(c("k")), float(c("lam"))
+        loss, grad, w, undecided = reference64(o, g, e, k, lam)
+        _, _, w_plain, _ = reference64(o, g, None, k, lam)
+        r = residual32(o, g)
+        assert r.dtype == np.float32 and np.array_equal(r, c("r")), i
+        assert np.array_equal(mask32(o, g, e).numpy(), c("mask")), i
+        assert np.array_equal((w == 0).numpy() & (c("w_plain") > 0), c("mask") & (c("w_plain") > 0)), i
+        V, _ = local_variance64(torch.from_numpy(c("r")), k)
+        for mine, ref in ((w, c("w")), (w_plain, c("w_plain")), (V, c("local"))):
+            assert mine.shape == ref.shape and mine.dtype == torch.float64
+            assert np.abs(mine.numpy() - ref).max() <= 1e-6 * max(np.abs(ref).max(), 1e-30), i
+        assert abs(float(loss) - float(c("loss"))) <= 1e-6 * abs(float(c("loss"))), i
+        gr, gref = grad.numpy(), c("grad")
+        assert np.array_equal(np.isnan(gr), np.isnan(gref)), i
+        fin = ~np.isnan(gref)
+        saw_nan |= bool((~fin).any())
+        assert np.abs(gr[fin] - gref[fin]).max() <= 1e-6 * np.abs(gref[fin]).max(), i
+        assert undecided.shape == c("mask").shape and undecided.dtype == torch.bool
+        # the map's backward for an upstream gradient and the local variance's: against the fp32 restatement's autograd
+        up = torch.randn(c("w").shape, generator=torch.Generator().manual_seed(i))
+        _, gmap, _, _ = reference64(o, g, e, k, upstream=up)
+        y = o.clone().requires_grad_(True)
+        restated_map(y, g, e, k)[0].backward(up)
+        fin = ~torch.isnan(y.grad)
+        assert torch.equal(torch.isnan(gmap), ~fin), i
+        if fin.any():
+            assert float((gmap - y.grad)[fin].abs().max()) <= 1e-5 * float(y.grad[fin].abs().max()), i
+    assert saw_nan
+
+
 def test_fixture_covers_the_traps(golden):
     """The fixture holds what the GPU tests lean on: every k of 3, 7, 9; the 4 x 5 image; pixels with r == r_e exactly
-    (not masked: the test is strict) and masked pixels; an image whose output equals its GT."""
+    (not masked: the test is strict) and masked pixels; an image whose output equals its GT.  Masked pixels with
+    r = 0 exist, but only inside that image (r = 0 < r_e everywhere, gradient all NaN): a masked r = 0 next to finite
+    gradients is covered by kind `zeros` of test_gpu_ldl.py alone."""
     f = golden("f18_ldl_artifact")
     n = int(f["n_cases"])
     assert {int(f[f"c{i}_k"]) for i in range(n)} >= {3, 7, 9}
@@ -122,3 +164,4 @@ def test_fixture_covers_the_traps(golden):
     assert ties > 10 and all(not (f[f"c{i}_ties"] & f[f"c{i}_mask"]).any() for i in range(n))
     assert any(f[f"c{i}_mask"].any() for i in range(n))
     assert any((f[f"c{i}_o"] == f[f"c{i}_g"]).reshape(f[f"c{i}_o"].shape[0], -1).all(1).any() for i in range(n))
+    assert any(((f[f"c{i}_r"] == 0) & f[f"c{i}_mask"]).any() for i in range(n))

@@ -118,3 +118,20 @@ def test_two_launch_small_step_under_lds_poison(dev, word):
         tt.test_tiny_step_vs_oracle(dev, 3, 48, 56, 0.08, 0.1, True)
         tt.test_tiny_step_vs_oracle(dev, 1, 7, 9, 0.5, 0.2, True)
         tt.test_tiny_step_more_rows_than_workgroups_and_capacity_cut(dev)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("word", PATTERNS)
+def test_ldl_kernels_under_lds_poison(dev, word):
+    """ssg_ldl.hip stages the residual's halo (ldl_map), G / G mu and their row sums (ldl_grad) and the block sums in
+    LDS: a minimal-side image, a tile-edge image, 4 x 3 x 128 x 128 and get_local_weights with its backward under LDS
+    poison equal the product build bit for bit (the same sources and -ffp-contract=off, fixed-order sums; the
+    profiling switches touch the host side of a launch only)."""
+    import test_gpu_ldl as tl
+    want = tl.poison_cases()
+    with poisoned(word):
+        got = tl.poison_cases()
+    assert len(got) == len(want) == 14
+    for i, (a, b) in enumerate(zip(got, want)):
+        assert bool(torch.isfinite(b).all()), i
+        assert torch.equal(a, b), (i, float((a - b).abs().max()))
