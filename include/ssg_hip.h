@@ -63,6 +63,8 @@ typedef void *ssg_stream_t; /* hipStream_t */
 /* 6 (round 6): + ssg_set_tiny_step; default dense threshold 16. */
 /* 6, additive: + ssg_ldl_workspace_bytes, ssg_artifact_map, ssg_artifact_map_backward, ssg_ldl_loss, ssg_local_variance
  * (LDL's artifact map, section (F)); nothing existing changed, so the version number stays. */
+/* 6, additive: + ssg_bbl_workspace_bytes, ssg_bbl_search, ssg_bbl_loss, ssg_flat_mask (BebyGAN's best-buddy loss and
+ * flat mask, section (G)); again nothing existing changed. */
 int ssg_abi_version(void);
 const char *ssg_status_string(int status);
 /* Device-side refusals that no return value can carry (everything is asynchronous): waits for `stream`, then returns
@@ -491,6 +493,39 @@ int ssg_ldl_loss(const float *output, const float *gt, const float *ema /* nulla
 int ssg_local_variance(const float *residual, int B, int H, int W, int k, float *v_out /* nullable */,
                        const float *grad_v /* nullable */, float *grad_residual /* nullable */, void *workspace,
                        size_t workspace_bytes, ssg_stream_t stream);
+
+/* ---------------------------------------------------------------- (G) ----
+ * BebyGAN's best-buddy loss and flat mask (basicsr/models/bebyganssl_model.py:471-565 BBL.forward with its caller's
+ * L1Loss(p1, sel_p2) at :723-724, and get_flat_mask at :93-104), ssl_amd/csrc/ssg_bbl.hip.  x, gt (B,C,H,W) fp32:
+ *   p1 = unfold(x, k, stride), p2 = unfold(gt, k, stride)                        (B, N, d), d = C k^2
+ *   cand = cat[p2, unfold(gt_2), unfold(gt_4)]                                   (B, M, d)
+ *     gt_2, gt_4: bicubic 1/2 and 1/4 of gt (A = -0.75, align_corners = False, no antialias, side floor(side / 2 | / 4))
+ *   ind_i = argmin_j alpha |p1_i - cand_j|^2 + beta |p2_i - cand_j|^2, evaluated in fp32 as
+ *           (alpha + beta) |cand_j|^2 - 2 (alpha p1_i + beta p2_i) . cand_j; among equal fp32 scores the LOWEST j wins,
+ *           so results are bit-reproducible
+ *   sel_p2_i = cand[ind_i];  loss = loss_weight * mean |p1 - sel_p2| (mean != 0; the sum otherwise)
+ *   grad_x = d loss / d x: loss_weight / (B N d) sgn(p1 - sel_p2) at each patch element's pixel, 0 at pixels outside the
+ *           patch grid (every pixel is written); sgn(0) = 0.  gt carries no gradient.
+ * Native domain: pad = 0, stride >= k >= 1, d <= 31, alpha, beta >= 0 with alpha + beta > 0.  Status: SSG_E_BADARG for a
+ * null pointer (those marked nullable excepted), B, C, H, W or k <= 0, stride < k, a negative or NaN weight or
+ * alpha + beta = 0; SSG_E_TOOLARGE for d > 31, B > 65535 or 2^31 elements and more; SSG_E_IMAGESMALL when gt_4 is
+ * smaller than k on a side (H / 4 < k or W / 4 < k: the reference's unfold raises); SSG_E_WORKSPACE for workspace_bytes <
+ * ssg_bbl_workspace_bytes(...) (which returns 0 for a shape outside the domain); SSG_E_ALIGN for a workspace that is
+ * not 16-byte aligned.  Three launches (four with the loss), no atomics, no score matrix, fixed summation orders.
+ * ssg_bbl_search: ind_out int32 (B,N); p1_out, sel_out (B,N,d), each nullable.
+ * ssg_bbl_loss: loss_out[0]; grad_x (B,C,H,W) and ind_out (B,N), each nullable.
+ * ssg_flat_mask: img (B,3,H,W); L = (0.2989 r + 0.587 g) + 0.114 b, reflect-padded by k / 2; mask_out (B,1,H,W) = 1.0
+ *   where the unbiased standard deviation of the k x k window is < thresh, else 0.0.  k odd, 3 <= k <= 15 (11 is the
+ *   compiled fast path).  SSG_E_BADARG for a null pointer, k even or < 3, B, H or W <= 0; SSG_E_TOOLARGE for k > 15;
+ *   SSG_E_IMAGESMALL for H or W <= k / 2 (torch's reflect pad raises).  One launch. */
+size_t ssg_bbl_workspace_bytes(int B, int C, int H, int W, int k, int stride);
+int ssg_bbl_search(const float *x, const float *gt, int B, int C, int H, int W, int k, int stride, float alpha,
+                   float beta, int *ind_out, float *p1_out /* nullable */, float *sel_out /* nullable */,
+                   void *workspace, size_t workspace_bytes, ssg_stream_t stream);
+int ssg_bbl_loss(const float *x, const float *gt, int B, int C, int H, int W, int k, int stride, float alpha,
+                 float beta, float loss_weight, int mean, float *loss_out, float *grad_x /* nullable */,
+                 int *ind_out /* nullable */, void *workspace, size_t workspace_bytes, ssg_stream_t stream);
+int ssg_flat_mask(const float *img, int B, int H, int W, int k, float thresh, float *mask_out, ssg_stream_t stream);
 
 #ifdef SSG_PROFILE
 /* PROFILING BUILD ONLY (libssg_hip_prof.so, compiled with -DSSG_PROFILE; the product library libssg_hip.so does not

@@ -584,3 +584,126 @@ class _LocalVarFn(torch.autograd.Function):
 def local_variance(residual, ksize):
     """get_local_weights(residual, ksize): (B,C,H,W) -> (B,C,H,W), differentiable with respect to `residual`."""
     return _LocalVarFn.apply(residual, ksize)
+
+
+# ------------------------------------------------- BebyGAN's best-buddy loss and flat mask (ssg_bbl.hip) ----
+def _bbl_prepare(x, gt, alpha, beta, ksize, stride):
+    """fp32 contiguous copies of (x, gt) after the checks every best-buddy entry point makes."""
+    _need_gpu(x, gt)
+    if gt.requires_grad:
+        raise ValueError("ssl_amd: the best-buddy loss is differentiable with respect to the output only, but `gt` "
+                         "requires grad; detach it (the reference's caller passes it without a gradient)")
+    if x.dim() != 4 or gt.shape != x.shape:
+        raise ValueError(f"ssl_amd: x and gt must be (B,C,H,W) of one shape, got {tuple(x.shape)}, {tuple(gt.shape)}")
+    ksize, stride = int(ksize), int(stride)
+    if stride < ksize:
+        raise NotImplementedError(f"ssl_amd: the best-buddy search needs stride >= ksize (patches that do not "
+                                  f"overlap), got ksize={ksize}, stride={stride}")
+    if x.shape[1] * ksize * ksize > 31:
+        raise NotImplementedError(f"ssl_amd: the best-buddy search holds a patch of at most 31 elements, got "
+                                  f"C*ksize^2 = {x.shape[1] * ksize * ksize}")
+    if not (alpha >= 0 and beta >= 0 and alpha + beta > 0):
+        raise ValueError(f"ssl_amd: the best-buddy weights must be non-negative and not both zero, got alpha={alpha}, "
+                         f"beta={beta}")
+    return _f32c(x), _f32c(gt), ksize, stride
+
+
+def _bbl_workspace(B, C, H, W, k, s, dev):
+    n = _lib.lib().ssg_bbl_workspace_bytes(B, C, H, W, k, s)
+    return torch.empty(max(n, 1), dtype=torch.uint8, device=dev), n
+
+
+def _bbl_patches(H, W, k, s):
+    return ((H - k) // s + 1) * ((W - k) // s + 1)
+
+
+def bbl_search(x, gt, alpha=1.0, beta=1.0, ksize=3, stride=3, want_p1=True, want_sel=True):
+    """BBL.forward's search (bebyganssl_model.py:541-565) without autograd: (ind int32 (B,N), p1, sel_p2 (B,N,d));
+    ind indexes cat[p2, unfold(gt_2), unfold(gt_4)], the lowest index among equal fp32 scores."""
+    xs, gs, k, s = _bbl_prepare(x, gt, alpha, beta, ksize, stride)
+    B, C, H, W = xs.shape
+    ws, nb = _bbl_workspace(B, C, H, W, k, s, xs.device)
+    N, d = max(_bbl_patches(H, W, k, s), 0), C * k * k
+    ind = torch.empty((B, N), dtype=torch.int32, device=xs.device)
+    p1 = torch.empty((B, N, d), dtype=torch.float32, device=xs.device) if want_p1 else None
+    sel = torch.empty((B, N, d), dtype=torch.float32, device=xs.device) if want_sel else None
+    with torch.cuda.device(xs.device):
+        _lib.check(_lib.lib().ssg_bbl_search(_ptr(xs), _ptr(gs), B, C, H, W, k, s, float(alpha), float(beta),
+                                             _ptr(ind), _ptr(p1), _ptr(sel), _ptr(ws), nb, _stream()))
+    return ind, p1, sel
+
+
+class _BBLPatchesFn(torch.autograd.Function):
+    """(p1, sel_p2) of BBL.forward.  p1 = unfold(x) is differentiable with respect to x: with stride >= ksize its
+    backward, the fold, moves every patch element to the one pixel it came from (no sums).  sel_p2 carries none (the
+    reference's comes from gt alone; min passes no gradient through its indices)."""
+
+    @staticmethod
+    def forward(ctx, x, gt, alpha, beta, k, s):
+        _, p1, sel = bbl_search(x, gt, alpha, beta, k, s)
+        ctx.geom = (tuple(x.shape), int(k), int(s))
+        ctx.in_dtype = x.dtype
+        ctx.mark_non_differentiable(sel)
+        return p1.to(x.dtype), sel.to(x.dtype)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_p1, g_sel):
+        (B, C, H, W), k, s = ctx.geom
+        g = torch.nn.functional.fold(g_p1.to(torch.float32).permute(0, 2, 1), (H, W), kernel_size=k, stride=s)
+        return g.to(ctx.in_dtype), None, None, None, None, None
+
+
+def bbl_patches(x, gt, alpha=1.0, beta=1.0, ksize=3, stride=3):
+    """BBL(alpha, beta, ksize, 0, stride).forward(x, gt) -> (p1, sel_p2), both (B,N,d)."""
+    return _BBLPatchesFn.apply(x, gt, alpha, beta, ksize, stride)
+
+
+class _BBLLossFn(torch.autograd.Function):
+    """loss_weight * mean (or sum) |p1 - sel_p2|: ONE ssg_bbl_loss call produces the loss and d loss / d x together;
+    backward() only scales that gradient by the incoming one (the pattern of _LdlLossFn)."""
+
+    @staticmethod
+    def forward(ctx, x, gt, alpha, beta, k, s, loss_weight, mean):
+        xs, gs, k, s = _bbl_prepare(x, gt, alpha, beta, k, s)
+        B, C, H, W = xs.shape
+        loss = torch.empty(1, dtype=torch.float32, device=xs.device)
+        grad = torch.empty_like(xs) if ctx.needs_input_grad[0] else None
+        ws, nb = _bbl_workspace(B, C, H, W, k, s, xs.device)
+        with torch.cuda.device(xs.device):
+            _lib.check(_lib.lib().ssg_bbl_loss(_ptr(xs), _ptr(gs), B, C, H, W, k, s, float(alpha), float(beta),
+                                               float(loss_weight), int(bool(mean)), _ptr(loss), _ptr(grad), None,
+                                               _ptr(ws), nb, _stream()))
+        if grad is not None:
+            ctx.save_for_backward(grad)
+        ctx.in_dtype = x.dtype
+        return loss[0]
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        grad, = ctx.saved_tensors
+        return (grad * g.to(torch.float32).reshape(())).to(ctx.in_dtype), None, None, None, None, None, None, None
+
+
+def bbl_loss(x, gt, alpha=1.0, beta=1.0, ksize=3, stride=3, loss_weight=1.0, reduction='mean'):
+    """L1Loss(*BBL(alpha, beta, ksize, 0, stride).forward(x, gt)), fused: the caller's bebyganssl_model.py:723-724 in
+    one call.  reduction 'mean' or 'sum'."""
+    if reduction not in ('mean', 'sum'):
+        raise ValueError(f"ssl_amd: bbl_loss fuses the 'mean' and 'sum' reductions only, got {reduction!r}")
+    return _BBLLossFn.apply(x, gt, alpha, beta, ksize, stride, loss_weight, reduction == 'mean')
+
+
+def flat_mask(img, kernel_size=11, std_thresh=0.025):
+    """get_flat_mask(img, kernel_size, std_thresh, scale=1) (bebyganssl_model.py:93-104): (B,3,H,W) -> (B,1,H,W) of
+    0.0 / 1.0, no gradient."""
+    _need_gpu(img)
+    if img.dim() != 4 or img.shape[1] != 3:
+        raise ValueError(f"ssl_amd: get_flat_mask takes a (B,3,H,W) image, got {tuple(img.shape)}")
+    x = _f32c(img)
+    B, _, H, W = x.shape
+    mask = torch.empty((B, 1, H, W), dtype=torch.float32, device=x.device)
+    with torch.cuda.device(x.device):
+        _lib.check(_lib.lib().ssg_flat_mask(_ptr(x), B, H, W, int(kernel_size), float(std_thresh), _ptr(mask),
+                                            _stream()))
+    return mask.to(img.dtype)
