@@ -538,7 +538,7 @@ __device__ __forceinline__ void bwd_dense_body(const DenseBwdParams &p) {
           if (!chan_on(c)) continue;
           const float v = brow[c * RWS + col];
           brow[c * RWS + col] = 0.f;
-          if (ok && v != 0.f && !SSG_DBG(p, 8)) grad_add(p.grad, p.gfix, (((size_t)b * C + c) * H + gy) * W + gx, 2.f * v, gsc);
+          if (ok && v != 0.f && !SSG_DBG(p, 8)) grad_add_wide(p.grad, p.gfix, (((size_t)b * C + c) * H + gy) * W + gx, 2.f * v, gsc);
         }
       }
     }
@@ -1000,7 +1000,7 @@ __device__ __forceinline__ void bwd_dense_body(const DenseBwdParams &p) {
         if (!chan_on(c)) continue;
         const float iuc = c == 0 ? iuA[i].x : c == 1 ? iuA[i].y : iuB[i], guc = c == 0 ? guA[i].x : c == 1 ? guA[i].y : guB[i];
         const float v = __builtin_fmaf(iuc, vt, guc);
-        if (ok && v != 0.f && !SSG_DBG(p, 8)) grad_add(p.grad, p.gfix, (((size_t)b * C + c) * H + gy) * W + gx, 2.f * v, gsc);
+        if (ok && v != 0.f && !SSG_DBG(p, 8)) grad_add_wide(p.grad, p.gfix, (((size_t)b * C + c) * H + gy) * W + gx, 2.f * v, gsc);
       }
     }
   }

@@ -293,12 +293,37 @@ inline int ensure_dynamic_lds(K kernel, int bytes, std::atomic<unsigned long lon
 // Deterministic mode (gfix != nullptr): the contribution is rounded to a multiple of 1/scale and added with a 64-bit
 // INTEGER atomic; integer addition is associative, so the sum does not depend on the order and two runs agree bit
 // for bit.  The scale is a power of two derived ON THE DEVICE from an upper bound of |G| = |dL/dD| (exact maximum
-// from ssg_grad_rows for ssg_map_backward and the tile-major step; the a-priori bound of the loss steps otherwise), stored as float bits in the word after the
-// n = B*C*H*W sums: |G| * scale < 2^36.  A pixel collects fewer than 2^21 terms 2 G d (2 k_w^2 k_s^2 = 8.1e5 for
-// (49,13) under a dense mask, 1.0e5 for (25,9)), so the sum stays below 2^36 * 2^21 * 2 |d| = 2^58 |d|: no wrap for
-// pixel differences up to 16 -- the loss is applied to the un-clamped generator output, whose differences exceed 1
-// early in training but not by that much.  Resolution: 2^-35 of the largest |G|, 11 bits finer than an fp32 sum of
-// the same terms.  (Round 2 used 2^-38, which left a factor 4 for |d| at (49,13).)
+// from ssg_grad_rows / ssg_rows_tm for ssg_map_backward and the k_s = 49 step with tile-major regions; the a-priori
+// bound of the loss steps otherwise), stored as float bits in the word after the n = B*C*H*W sums:
+// |G| * scale < 2^36, and >= 2^35 for the largest |G| when the bound is exact.  Resolution: 2^-35 of the largest |G|,
+// 11 bits finer than an fp32 sum of the same terms.  (Round 2 used 2^-38.)
+//
+// Two ranges limit the format, and the SECOND is the binding one:
+//  (1) the 64-bit sum of a pixel.  A pixel collects fewer than 2^21 terms 2 G d (2 k_w^2 k_s^2 = 8.1e5 for (49,13)
+//      under a dense mask, 1.0e5 for (25,9)), so the sum stays below 2^36 * 2^21 * 2 |d| = 2^58 |d|: no wrap for pixel
+//      differences up to 16 -- the loss is applied to the un-clamped generator output, whose differences exceed 1
+//      early in training but not by that much.
+//  (2) the single conversion.  What a caller hands over is already a SUM of such terms, formed in fp32, and the
+//      conversion has to hold it -- how many terms is a property of the caller:
+//        direct kernels (ssg_bwd.hip), ssg_tiny.hip: the terms of ONE row (of up to 5 merged rows) that meet in one
+//          pixel -- at most k_w^2 at a tile position, k_s^2 at a window position: |v * scale| <= 5 * 2 k_s^2 |d| * 2^36
+//          = 2^50.6 |d| at (49,13) if every G of the rows had the largest magnitude and one sign.  A normalised row's G
+//          changes sign (its sum over the offsets is ~0) and decays away from the centre: far below.  fix_round() holds
+//          these.
+//        dense-tile backward (ssg_bwd_dense.hip: flush_row and the tile's own pixels): the sum over ALL edge pixels of
+//          the tile (128 / 256) and all offset rows of the wave -- every one of the k_s^2 offsets when the plan holds
+//          more tiles than the device has wave slots (qsplit 1: the full-size dense-mask step).  On coherent content
+//          (a step edge: every pixel of a tile sees the edge on the same side) the fp64 oracle gives 2^15.5 |G|max for
+//          such a sum at (49,13), sigma 1: |v * scale| = 2^50.5 .. 2^51.5 under an exact bound, by where |G|max falls
+//          in its binade.  Splitting the offset rows over several waves does not shrink what a wave converts (the
+//          wave of the first part adds the tile's border sums sum_b for ALL offsets, every wave subtracts its own
+//          share: the pieces cancel across waves only).  Beyond 2^51 fix_round() does not saturate: it returns
+//          2^51 + (excess / 2).  Measured: 1.5e-2 of max|grad| off at one wave per tile, 6e-2 to 1.4e-1 with the rows
+//          split 5 to 25 ways (tests/test_gpu_fix_range.py, profiles/fix_range.txt).  These sums go through
+//          grad_add_wide(), whose conversion is valid for the whole int64 range; below 2^51 both conversions are
+//          round-half-even of the same exact product and return the same bits.
+//      The 2^58 |d| budget of (1) says nothing about (2): a sum far inside it may still consist of ONE value that
+//      fix_round() cannot convert.
 __device__ __forceinline__ float grad_fix_scale_of(unsigned bound_bits) {
   unsigned e = (bound_bits >> 23) & 0xffu;   // biased exponent of the bound: bound < 2^(e-126)
   e = e < 40u ? 40u : e;
@@ -319,8 +344,10 @@ __device__ __forceinline__ float loss_grad_bound(float sigma, int C, int kw, flo
 }
 // round(v * scale) as a 64-bit integer, round-half-even like __float2ll_rn(v * scale) (the product is exact: scale is a
 // power of two), through the double "magic number": x + 1.5 * 2^52 leaves the integer in the low mantissa bits for
-// |x| < 2^51 -- a contribution is below 2^36 * a few dozen terms.  Four instructions (two of them fp64) instead of the
-// twelve of the fp32 -> i64 conversion sequence: the conversion was 2-3 % of both backward kernels' instructions.
+// |x| < 2^51 ONLY (outside, the exponent of the sum changes and the low bits no longer hold the integer: no saturation,
+// a wrong value) -- per-row terms, see (2) above; whole-tile sums take grad_add_wide().  Four instructions (two of them
+// fp64) instead of the twelve of the fp32 -> i64 conversion sequence: the conversion was 2-3 % of both backward kernels'
+// instructions.
 __device__ __forceinline__ long long fix_round(float v, float scale) {
   const double x = __builtin_fma((double)v, (double)scale, 6755399441055744.0);   // 1.5 * 2^52
   return __double_as_longlong(x) - 0x4338000000000000LL;
@@ -328,6 +355,15 @@ __device__ __forceinline__ long long fix_round(float v, float scale) {
 __device__ __forceinline__ void grad_add(float *grad, long long *gfix, size_t idx, float v, float scale) {
   if (gfix)
     atomicAdd((unsigned long long *)gfix + idx, (unsigned long long)fix_round(v, scale));
+  else
+    unsafeAtomicAdd(grad + idx, v);
+}
+// The same for a value that is a whole tile's sum (the dense-tile backward's flushes, see above): v_cvt_f64_f32,
+// v_mul_f64 (exact: the scale is a power of two), then the fp64 -> i64 conversion sequence, round-half-even, valid while
+// |v * scale| < 2^63.  About 1.7e4 conversions per tile against 3e7 lane-instructions of tile work.
+__device__ __forceinline__ void grad_add_wide(float *grad, long long *gfix, size_t idx, float v, float scale) {
+  if (gfix)
+    atomicAdd((unsigned long long *)gfix + idx, (unsigned long long)__double2ll_rn((double)v * (double)scale));
   else
     unsafeAtomicAdd(grad + idx, v);
 }
