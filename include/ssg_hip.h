@@ -527,6 +527,36 @@ int ssg_bbl_loss(const float *x, const float *gt, int B, int C, int H, int W, in
                  int *ind_out /* nullable */, void *workspace, size_t workspace_bytes, ssg_stream_t stream);
 int ssg_flat_mask(const float *img, int B, int H, int W, int k, float thresh, float *mask_out, ssg_stream_t stream);
 
+/* ---------------------------------------------------------------- (H) ----
+ * BebyGAN's back-projection loss and the imresize under it (basicsr/models/bebyganssl_model.py:727-731:
+ * l_pix_bp = L1Loss(imresize(output, scale = 1 / s), lq); imresize at :375-469 on its integer-factor path,
+ * discrete_kernel -> downsampling_2d, :133-162 and :351-373), ssl_amd/csrc/ssg_bp.hip.  x (planes,H,W) fp32 planes
+ * (planes = B C); s the integer factor, 2, 3 or 4; K = 4s (s even) or 4s - 1 (s odd); p = (K - s) / 2:
+ *   taps  w_i = c(r_i) / sum_j c(r_j), r_i = (i - (K-1)/2) / s, c the Keys cubic with a = -0.5 (MATLAB's antialiased
+ *         bicubic), formed in fp64 and rounded once to fp32; the 2-D tap is w_i w_j
+ *   pad   symmetric, p pixels per side: index -1-i reads pixel i, n+i reads n-1-i (the edge pixel is used twice)
+ *   y[oy,ox] = sum_{i,j<K} w_i w_j x~[s oy + i - p, s ox + j - p], (planes,h,w) with h = H / s, w = W / s (floor)
+ *   loss  = loss_weight * mean |y - lq| over the planes h w elements (mean != 0; the sum otherwise)
+ *   grad_x = d loss / d x = loss_weight / M K^T sgn(y - lq), K^T the exact adjoint of the padding and the strided
+ *         correlation (a pixel under one or both mirrors collects each of its padded copies); sgn(0) = 0; every pixel
+ *         is written.  lq carries no gradient.
+ * Status, decided before any launch: SSG_E_BADARG for a null pointer (those marked nullable excepted), planes, H or
+ * W <= 0, s < 2 or a NaN loss_weight; SSG_E_TOOLARGE for s > 4 or 2^31 elements and more; SSG_E_IMAGESMALL for H or
+ * W < p (the reference's padding loop raises); SSG_E_WORKSPACE for workspace_bytes < ssg_bp_workspace_bytes(...)
+ * (which returns 0 for a shape outside the domain; it holds the signs and at most 4,096 partial sums: at most
+ * 2 planes h w 4 bytes + 64 KiB, nothing of input size); SSG_E_ALIGN for a workspace that is not 16-byte aligned.
+ * No atomics, fixed summation orders (bit-reproducible), no allocation, synchronisation or host read.
+ * ssg_bp_downsample: y_out (planes,h,w); one launch.
+ * ssg_bp_downsample_backward: grad_x (planes,H,W) = K^T grad_y (overwritten); one launch.
+ * ssg_bp_loss: loss_out[0]; grad_x (planes,H,W) and y_out (planes,h,w), each nullable; two launches. */
+size_t ssg_bp_workspace_bytes(int planes, int H, int W, int s);
+int ssg_bp_downsample(const float *x, int planes, int H, int W, int s, float *y_out, ssg_stream_t stream);
+int ssg_bp_downsample_backward(const float *grad_y, int planes, int H, int W, int s, float *grad_x,
+                               ssg_stream_t stream);
+int ssg_bp_loss(const float *x, const float *lq, int planes, int H, int W, int s, float loss_weight, int mean,
+                float *loss_out, float *grad_x /* nullable */, float *y_out /* nullable */, void *workspace,
+                size_t workspace_bytes, ssg_stream_t stream);
+
 #ifdef SSG_PROFILE
 /* PROFILING BUILD ONLY (libssg_hip_prof.so, compiled with -DSSG_PROFILE; the product library libssg_hip.so does not
  * export this symbol and has no code path that skips work).  Results are WRONG while a mask is set: skip kernel

@@ -72,6 +72,10 @@ PROTOTYPES = {
     "ssg_bbl_search": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _f, _f, _vp, _vp, _vp, _vp, _sz, _vp]),
     "ssg_bbl_loss": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _f, _f, _f, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     "ssg_flat_mask": (_i, [_vp, _i, _i, _i, _i, _f, _vp, _vp]),
+    "ssg_bp_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "ssg_bp_downsample": (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),
+    "ssg_bp_downsample_backward": (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),
+    "ssg_bp_loss": (_i, [_vp, _vp, _i, _i, _i, _i, _f, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
     # include/similarity.h: the reference operator's own (void, stream-less) interface
     "ssg_ref_compute_similarity": (None, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i]),
     "ssg_ref_compute_similarity_backward": (None, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i]),

@@ -707,3 +707,107 @@ def flat_mask(img, kernel_size=11, std_thresh=0.025):
         _lib.check(_lib.lib().ssg_flat_mask(_ptr(x), B, H, W, int(kernel_size), float(std_thresh), _ptr(mask),
                                             _stream()))
     return mask.to(img.dtype)
+
+
+# ------------------------------------------- BebyGAN's back-projection loss and its imresize (ssg_bp.hip) ----
+def _bp_pad(s):
+    """Pixels of symmetric padding per side at factor s: (K - s) // 2 with K = 4s (s even) or 4s - 1 (s odd)."""
+    return ((4 * s if s % 2 == 0 else 4 * s - 1) - s) // 2
+
+
+def _bp_prepare(x, lq, s):
+    """The fp32 contiguous copy of x (and of lq) after the checks every back-projection entry point makes; x is
+    (..., H, W) with any number of leading plane dimensions."""
+    _need_gpu(x, lq)
+    s = int(s)
+    if s not in (2, 3, 4):
+        raise NotImplementedError(f"ssl_amd: the antialiased bicubic downsampling runs the integer factors 2, 3 and 4 "
+                                  f"only, got {s}")
+    if x.dim() < 2 or not x.dtype.is_floating_point:
+        raise ValueError(f"ssl_amd: expected a floating tensor of at least two dimensions, got {tuple(x.shape)} "
+                         f"{x.dtype}")
+    H, W = x.shape[-2:]
+    if x.numel() == 0:
+        raise ValueError(f"ssl_amd: an empty tensor of shape {tuple(x.shape)} holds no image to downsample")
+    if min(H, W) < _bp_pad(s):
+        raise ValueError(f"ssl_amd: an image of {H} x {W} is smaller than the {_bp_pad(s)} pixels of symmetric padding "
+                         f"at factor {s} (the reference's padding loop raises IndexError)")
+    if lq is not None:
+        if lq.requires_grad:
+            raise ValueError("ssl_amd: the back-projection loss is differentiable with respect to the output only, "
+                             "but `lq` requires grad; detach it (the reference's caller passes it without a gradient)")
+        if tuple(lq.shape) != tuple(x.shape[:-2]) + (H // s, W // s):
+            raise ValueError(f"ssl_amd: lq must be {tuple(x.shape[:-2]) + (H // s, W // s)} for an output of "
+                             f"{tuple(x.shape)} at factor {s}, got {tuple(lq.shape)}")
+        lq = _f32c(lq)
+    return _f32c(x), lq, s
+
+
+class _BPDownsampleFn(torch.autograd.Function):
+    """y = imresize(x, 1 / s) on the discrete-kernel path; backward: one ssg_bp_downsample_backward call (the exact
+    adjoint of symmetric padding + strided correlation) for any upstream dL/dy."""
+
+    @staticmethod
+    def forward(ctx, x, s):
+        xs, _, s = _bp_prepare(x, None, s)
+        H, W = xs.shape[-2:]
+        P = xs.numel() // (H * W)
+        y = torch.empty(tuple(xs.shape[:-2]) + (H // s, W // s), dtype=torch.float32, device=xs.device)
+        with torch.cuda.device(xs.device):
+            _lib.check(_lib.lib().ssg_bp_downsample(_ptr(xs), P, H, W, s, _ptr(y), _stream()))
+        ctx.geom, ctx.in_dtype = (tuple(xs.shape), P, s), x.dtype
+        return y.to(x.dtype)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_y):
+        shape, P, s = ctx.geom
+        gy = _f32c(grad_y)
+        grad = torch.empty(shape, dtype=torch.float32, device=gy.device)
+        with torch.cuda.device(gy.device):
+            _lib.check(_lib.lib().ssg_bp_downsample_backward(_ptr(gy), P, shape[-2], shape[-1], s, _ptr(grad),
+                                                             _stream()))
+        return grad.to(ctx.in_dtype), None
+
+
+def bp_downsample(x, s):
+    """MATLAB's antialiased bicubic 1/s of (..., H, W) -> (..., H // s, W // s), s in {2, 3, 4}: the reference's
+    imresize(x, scale=1 / s) (bebyganssl_model.py:375-469), differentiable with respect to x.  Computed in fp32
+    whatever the floating dtype of x, and cast back."""
+    return _BPDownsampleFn.apply(x, s)
+
+
+class _BPLossFn(torch.autograd.Function):
+    """loss_weight * mean (or sum) |imresize(x, 1 / s) - lq|: ONE ssg_bp_loss call produces the loss and d loss / d x
+    together; backward() only scales that gradient by the incoming one (the pattern of _BBLLossFn)."""
+
+    @staticmethod
+    def forward(ctx, x, lq, s, loss_weight, mean):
+        xs, ls, s = _bp_prepare(x, lq, s)
+        H, W = xs.shape[-2:]
+        P = xs.numel() // (H * W)
+        loss = torch.empty(1, dtype=torch.float32, device=xs.device)
+        grad = torch.empty_like(xs) if ctx.needs_input_grad[0] else None
+        nb = _lib.lib().ssg_bp_workspace_bytes(P, H, W, s)
+        ws = torch.empty(max(nb, 1), dtype=torch.uint8, device=xs.device)
+        with torch.cuda.device(xs.device):
+            _lib.check(_lib.lib().ssg_bp_loss(_ptr(xs), _ptr(ls), P, H, W, s, float(loss_weight), int(bool(mean)),
+                                              _ptr(loss), _ptr(grad), None, _ptr(ws), nb, _stream()))
+        if grad is not None:
+            ctx.save_for_backward(grad)
+        ctx.in_dtype = x.dtype
+        return loss[0]
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        grad, = ctx.saved_tensors
+        return (grad * g.to(torch.float32).reshape(())).to(ctx.in_dtype), None, None, None, None
+
+
+def bp_loss(x, lq, s=4, loss_weight=1.0, reduction='mean'):
+    """L1Loss(imresize(x, scale=1 / s), lq), fused: the caller's bebyganssl_model.py:727-731 in one call.  reduction
+    'mean' or 'sum'."""
+    if reduction not in ('mean', 'sum'):
+        raise ValueError(f"ssl_amd: bp_loss fuses the 'mean' and 'sum' reductions only, got {reduction!r}")
+    return _BPLossFn.apply(x, lq, s, loss_weight, reduction == 'mean')

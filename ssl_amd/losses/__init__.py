@@ -1,4 +1,4 @@
 from .basic_loss import ArtifactLoss, KLDistanceLoss, L1Loss, SSGLoss, set_native_criteria  # noqa: F401
 from .loss_util import get_artifact_map, get_local_weights, get_refined_artifact_map, similarity_map  # noqa: F401
 from .lazy import LazySSG, lazy_enabled, set_lazy  # noqa: F401
-from .bebygan import BBL, BestBuddyLoss, get_flat_mask  # noqa: F401
+from .bebygan import BBL, BackProjectionLoss, BestBuddyLoss, get_flat_mask, imresize  # noqa: F401
