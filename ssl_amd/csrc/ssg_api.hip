@@ -7,86 +7,7 @@
 #include <cstdlib>
 #include <mutex>
 
-#include "ssg_common.hpp"
-
-namespace ssg {
-int launch_fwd(const FwdParams &p, hipStream_t st);
-int launch_bwd(const BwdParams &p, hipStream_t st);
-unsigned bwd_grid(const BwdParams &p);
-size_t bwd_max_partials(int B, int H, int W, int n_rows);
-int launch_loss_finalize(const LossFinalize &f, hipStream_t st);
-const char *fwd_kernel_name(int ks, int kw);
-const char *bwd_kernel_name(int ks, int kw);
-size_t edge_scratch_bytes(int B, int H, int W);
-int launch_edge_list(const void *mask, int kind, int mask_channels, int B, int H, int W, int stride, float thr,
-                     int *edges, int capacity, int *counts, int *rank, int *order, int *plan, int dense_thr,
-                     int plan_tile_rows, void *scratch, void *zero_a, size_t zero_a_bytes, void *zero_b,
-                     size_t zero_b_bytes, void *zero_c, size_t zero_c_bytes, hipStream_t st);
-size_t fwd_plan_bytes(int B, int H, int W, int capacity);
-int fwd_plan_order_offset(int B, int H, int W);
-struct DenseParams {
-  const float *img[2];
-  float *out[2];
-  int nimg;
-  const int *rank;
-  const int *n_dense;
-  const int *tiles;
-  int max_tiles;
-  const int *n_dev;
-  int n_host;
-  int B, H, W;
-  float sigma, eps;
-  int generalization;
-  int dbg;
-  double *row_scale;
-  float *tm[2];
-  int tm_slots;
-  int grid_tiles;
-  const int *strips;
-  int max_strips;
-  int *status;
-  int raw;
-};
-int fwd_plan_strip_offset(int B, int H, int W);
-int dense_max_strips(int B, int H, int W, int ks);
-bool dense_supported(int ks, int kw, int C);
-int dense_max_tiles(int B, int H, int W, int ks);
-int dense_tile_rows(int ks);
-int launch_fwd_dense(const DenseParams &p, int ks, int kw, int C, hipStream_t st);
-int launch_edge_mask(const float *gt, int B, int H, int W, float thr, int stride, uint8_t *out, hipStream_t st);
-bool grow_supported(int ks, int kw);
-unsigned grow_grid(int n_host);
-int launch_grad_rows(const GrowParams &p, int ks, int kw, hipStream_t st);
-int launch_rows_tm(const TmRowsParams &p, int ks, int kw, hipStream_t st);
-int rows_tm_parts(int n_tiles);
-int launch_pos_to_mask(const int *pos, int mc, int Hp, int Wp, uint8_t *mask, hipStream_t st);
-int launch_pos_relabel(const int *pos, int mc, int Hp, int Wp, int *rank, int *perm, int *dup, int *ndup, int *plan,
-                       int *order2, hipStream_t st);
-size_t criteria_scratch_bytes();
-int launch_criteria_sums(const float *a, const float *b, size_t n, void *scratch, float *sums_out, hipStream_t st);
-int launch_criteria_grad(const float *a, const float *b, size_t n, const float *coef, float *g, hipStream_t st);
-bool dense_bwd_supported(int ks, int kw, int C);
-int launch_bwd_dense(const DenseBwdParams &p, int ks, int kw, int C, hipStream_t st);
-int launch_augment_crop(const void *src, void *dst, int elem_bytes, int B, int C, int Hs, int Ws, int Ho, int Wo,
-                        const int *params, hipStream_t st);
-int launch_pool_swap(void *queue, void *batch, size_t sample_bytes, const int *slots, int b, hipStream_t st);
-size_t usm_scratch_bytes(int B, int C, int H, int W);
-int launch_jpeg(const float *img, float *out, int B, int H, int W, const float *quality_dev, float quality_host,
-                hipStream_t st);
-int launch_filter2d(const float *img, const float *kernels, float *out, int B, int C, int H, int W, int k, int nk,
-                    hipStream_t st);
-int launch_usm_sharp(const float *img, float *out, int B, int C, int H, int W, int ksize, float sigma, float weight,
-                     float threshold, void *scratch, hipStream_t st);
-int launch_grad_fix_flush(long long *gfix, float *grad, size_t n, int assign, hipStream_t st, const LossFinalize *fin = nullptr);
-int launch_grad_fix_bound(const BwdParams &p, hipStream_t st);
-int launch_grad_fix_reduce(const float *part, int n, long long *gfix, size_t n_fix, hipStream_t st);
-bool tiny_edge_list_ok(int B, int H, int W);
-int launch_tiny_edge_list(const void *mask, int kind, int mask_channels, int B, int H, int W, int stride, float thr,
-                          int *edges, int capacity, int *counts, int *rank, void *zero_a, size_t zero_a_bytes,
-                          void *zero_b, size_t zero_b_bytes, void *zero_c, size_t zero_c_bytes, hipStream_t st);
-bool tiny_step_supported(int ks, int kw, int C, int capacity);
-int launch_tiny_step(const TinyParams &p, int C, hipStream_t st);
-}  // namespace ssg
+#include "ssg_host.hpp"
 
 using namespace ssg;
 
@@ -102,15 +23,17 @@ using namespace ssg;
 // best); 10 costs Bernoulli 4 % 20 %.  Default 16.
 // ssg_set_dense_threshold(n) overrides it (profiling build: also the environment variable SSG_DENSE_THR at first use).
 constexpr int DENSE_THR_DEFAULT = 16;
-static std::atomic<int> g_dense_thr{-1};   // (atomic: the ABI may be called from several host threads)
-static int dense_threshold() {
-  int v = g_dense_thr.load(std::memory_order_relaxed);
-  if (v < 0) {
-    v = env_int("SSG_DENSE_THR", DENSE_THR_DEFAULT);
-    if (v < 0) v = 0;
-    g_dense_thr.store(v, std::memory_order_relaxed);
-  }
+// A process-wide setting behind a set function of the ABI: unset (negative) until its first read, which takes init() --
+// the default; in the profiling build an environment variable.  (atomic: the ABI may be called from several host threads)
+template <class Init>
+static int setting(std::atomic<int> &s, Init init) {
+  int v = s.load(std::memory_order_relaxed);
+  if (v < 0) s.store(v = init(), std::memory_order_relaxed);
   return v;
+}
+static std::atomic<int> g_dense_thr{-1};
+static int dense_threshold() {
+  return setting(g_dense_thr, [] { const int v = env_int("SSG_DENSE_THR", DENSE_THR_DEFAULT); return v < 0 ? 0 : v; });
 }
 
 // Small (11,5) steps in two launches (ssg_tiny.hip); on by default, ssg_set_tiny_step(0) keeps every call on the general path.
@@ -131,15 +54,8 @@ extern "C" int ssg_set_dense_threshold(int edge_pixels_per_tile) {
 #ifdef SSG_PROFILE
 static std::atomic<int> g_dbg{-1};
 static int dbg_mask() {
-  int v = g_dbg.load(std::memory_order_relaxed);
-  if (v < 0) {
-    v = env_int("SSG_DEBUG_SKIP", 0);
-    if (v < 0) v = 0;
-    g_dbg.store(v, std::memory_order_relaxed);
-  }
-  return v;
+  return setting(g_dbg, [] { const int v = env_int("SSG_DEBUG_SKIP", 0); return v < 0 ? 0 : v; });
 }
-namespace ssg { int strip_occupancy(); int strip_times(unsigned long long *host, int n); }
 // LDS poison (ssg_common.hpp): one workgroup per CU at a time (all 160 KB), several rounds so that every CU gets one
 static std::atomic<int> g_lds_poison_on{0};
 static std::atomic<unsigned> g_lds_poison_pat{0};
@@ -189,13 +105,15 @@ static std::atomic<int> g_overlap{-1};
 // 0 off, 1 dense-tile kernel on the caller's stream, 2 direct kernel on the caller's stream, 3 (default) whichever of the
 // two the previous plan built on this device makes the longer branch
 static int overlap_mode() {
-  int v = g_overlap.load(std::memory_order_relaxed);
-  if (v < 0) {
-    v = env_int("SSG_OVERLAP", 3);
-    v = v < 0 ? 0 : (v > 3 ? 3 : v);
-    g_overlap.store(v, std::memory_order_relaxed);
-  }
-  return v;
+  return setting(g_overlap, [] { const int v = env_int("SSG_OVERLAP", 3); return v < 0 ? 0 : (v > 3 ? 3 : v); });
+}
+
+// Index of the calling thread's current device in the library's per-device tables (plan hint, side stream, status word,
+// operator pool); -1: no current device, or one beyond the tables -- such a call runs without the table's service.
+constexpr int MAXDEV = 64;
+static int current_device_slot() {
+  int dev = 0;
+  return hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < MAXDEV ? dev : -1;
 }
 
 static bool stream_capturing(hipStream_t st) {
@@ -211,11 +129,10 @@ struct PlanHint {
   int *host = nullptr, *dev = nullptr;
 };
 static PlanHint plan_hint(bool allocate_never = false) {
-  constexpr int MAXDEV = 64;
   static std::mutex mu;
   static PlanHint tab[MAXDEV];
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= MAXDEV) return PlanHint{};
+  const int dev = current_device_slot();
+  if (dev < 0) return PlanHint{};
   std::lock_guard<std::mutex> lk(mu);
   if (!tab[dev].host) {
     // hipHostMalloc is not allowed while the calling stream is being captured (it fails, and in the global / thread-local
@@ -319,10 +236,9 @@ extern "C" int ssg_set_overlap(int mode) {
   return prev;
 }
 static SideStream *side_stream() {
-  constexpr int MAXDEV = 64;
   thread_local SideStream tab[MAXDEV];
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= MAXDEV) return nullptr;
+  const int dev = current_device_slot();
+  if (dev < 0) return nullptr;
   SideStream &s = tab[dev];
   if (!s.side) {
     if (hipStreamCreateWithFlags(&s.side, hipStreamNonBlocking) != hipSuccess ||
@@ -356,11 +272,10 @@ static int join_side(Schedule &s) {
 // kernels that refuse their input without a host-visible error -- a dense kernel handed a plan cut for another tile
 // height -- set a bit in it; ssg_device_status() reads and clears it.
 static int *device_status_word() {
-  constexpr int MAXDEV = 64;
   static std::mutex mu;
   static int *tab[MAXDEV] = {};
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= MAXDEV) return nullptr;
+  const int dev = current_device_slot();
+  if (dev < 0) return nullptr;
   std::lock_guard<std::mutex> lk(mu);
   if (!tab[dev]) {
     int *w = nullptr;
@@ -377,16 +292,16 @@ static int *device_status_word() {
 static bool sizes_ok(int ks, int kw) { return ks > 0 && kw > 0 && (ks & 1) && (kw & 1) && kw <= ks; }
 
 static size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+// lays the pieces of a buffer out one behind the other, each on a 256-byte boundary
+struct Carver {
+  size_t end = 0;
+  size_t take(size_t bytes) { return std::exchange(end, end + align_up(bytes, 256)); }
+};
 
 // Waves per tile of the dense-tile backward (each takes a contiguous range of offset rows): by default chosen on the
 // device so that the launch fills the chip about once; SSG_BWD_QSPLIT fixes it in the profiling build (experiments).
 static int bwd_qsplit() {   // 0 = chosen on the device from the number of dense tiles (DenseBwdParams::qsplit)
-  static int v = -1;
-  if (v < 0) {
-    v = env_int("SSG_BWD_QSPLIT", 0);
-    if (v < 0) v = 0;
-    if (v > 25) v = 25;
-  }
+  static const int env = env_int("SSG_BWD_QSPLIT", 0), v = env < 0 ? 0 : (env > 25 ? 25 : env);
   return v;
 }
 
@@ -406,18 +321,12 @@ struct TileMajor {
   int slots = 0;
 };
 static bool strips_enabled() {   // SSG_STRIPS=0: the tile kernel computes every tile-major tile (A/B measurements)
-  static int v = -1;
-  if (v < 0) {
-    v = env_int("SSG_STRIPS", 1) != 0;
-  }
-  return v != 0;
+  static const bool on = env_int("SSG_STRIPS", 1) != 0;
+  return on;
 }
 static bool tile_major_enabled() {
-  static int v = -1;
-  if (v < 0) {
-    v = env_int("SSG_TILE_MAJOR", 1) != 0;
-  }
-  return v != 0;
+  static const bool on = env_int("SSG_TILE_MAJOR", 1) != 0;
+  return on;
 }
 
 // nparts of a split backward's criteria sums: ssg_grad_rows' workgroups, then ssg_rows_tm's
@@ -445,6 +354,7 @@ static int split_backward(BwdParams p, const int *rank, const int *plan, void *s
   float *gmax_part = (float *)((char *)sum_b + nfl);
   float *dot = (float *)((char *)gmax_part + nfl);
   const int n_tm = split_tm_tiles(p, tm);
+  const PlanView pv = plan_view(plan, p.B, p.H, p.W);
   GrowParams g{};
   g.mode = p.mode;
   g.gin = p.gin;
@@ -466,9 +376,9 @@ static int split_backward(BwdParams p, const int *rank, const int *plan, void *s
   g.gmax_part = p.gfix ? gmax_part : nullptr;
   if (n_tm > 0) {   // (tile-major call: ssg_grad_rows walks the plan's list of sparse rows with a capped grid)
     g.grid_cap = 4096;
-    g.tm_hdr = plan + 1;
+    g.tm_hdr = pv.dense_hdr;
     g.tm_slots = tm->slots;
-    g.sparse_order = plan + fwd_plan_order_offset(p.B, p.H, p.W);
+    g.sparse_order = pv.sparse_order;
   }
   // GRAD_LOSS without tile-major rows (every k_s <= 25 call): the fixed-point scale comes from the a-priori bound of |G|
   // (ssg_grad_rows' first workgroup writes it: no maximum over the rows, no reduction launch); and with deferred row
@@ -499,9 +409,9 @@ static int split_backward(BwdParams p, const int *rank, const int *plan, void *s
       GrowParams gs = g;   // the plan's sparse list; its criteria sums behind the first pass's
       gs.only = 2;
       gs.grid_cap = 4096;
-      gs.tm_hdr = plan + 1;
+      gs.tm_hdr = pv.dense_hdr;
       gs.tm_slots = 0;
-      gs.sparse_order = plan + fwd_plan_order_offset(p.B, p.H, p.W);
+      gs.sparse_order = pv.sparse_order;
       gs.partials = p.partials + 2 * (size_t)grow_grid(p.n_host);
       if (!rc) rc = launch_grad_rows(gs, p.ks, p.kw, sc.direct());
     } else {
@@ -514,8 +424,8 @@ static int split_backward(BwdParams p, const int *rank, const int *plan, void *s
     t.tm[1] = tm->rows[1];
     t.row_scale = p.row_scale;
     t.rank = rank;
-    t.n_dense = plan + 1;
-    t.tiles = plan + 4;
+    t.n_dense = pv.dense_hdr;
+    t.tiles = pv.tiles;
     t.n_tiles = n_tm;
     t.tm_slots = tm->slots;
     t.n_dev = p.n_dev;
@@ -551,8 +461,8 @@ static int split_backward(BwdParams p, const int *rank, const int *plan, void *s
   d.G = grows;
   d.sum_b = sum_b;
   d.rank = rank;
-  d.n_dense = plan + 1;
-  d.tiles = plan + 4;
+  d.n_dense = pv.dense_hdr;
+  d.tiles = pv.tiles;
   d.max_tiles = dense_max_tiles(p.B, p.H, p.W, p.ks);
   d.n_dev = p.n_dev;
   d.n_host = p.n_host;
@@ -592,8 +502,8 @@ static int split_backward(BwdParams p, const int *rank, const int *plan, void *s
     BwdParams s = p;
     s.mode = GRAD_D;
     s.gin = grows;
-    s.order = plan + fwd_plan_order_offset(p.B, p.H, p.W);
-    s.n_dev = plan;  // n_sparse
+    s.order = pv.sparse_order;
+    s.n_dev = pv.n_sparse;
     s.partials = nullptr;
     s.rows_hint = sc.rows_hint;
     rc = launch_bwd(s, sc.direct());
@@ -608,12 +518,14 @@ static int split_backward(BwdParams p, const int *rank, const int *plan, void *s
 }
 
 // Deterministic mode: the kernels add into the caller's zeroed fixed-point buffer; one flush folds it into grad.
+// the fixed-point gradient sums of a (B,C,H,W) image and, behind them, the word with the bound of |G| (8 sums' room)
+static size_t grad_fix_bytes(int B, int C, int H, int W) { return sizeof(long long) * ((size_t)B * C * H * W + 8); }
 static int det_begin(BwdParams &p, void *grad_fix, hipStream_t st, bool prezeroed = false) {
   p.gfix = nullptr;
   if (!grad_fix || !p.grad) return 0;
   p.gfix = (long long *)grad_fix;
   if (prezeroed) return 0;   // (the fused step: cleared by the edge-list builder's first kernel)
-  return (int)hipMemsetAsync(grad_fix, 0, sizeof(long long) * ((size_t)p.B * p.C * p.H * p.W + 8), st);
+  return (int)hipMemsetAsync(grad_fix, 0, grad_fix_bytes(p.B, p.C, p.H, p.W), st);
 }
 static int det_end(const BwdParams &p, hipStream_t st, bool assign = false, const LossFinalize *fin = nullptr, bool *fin_done = nullptr) {
   if (!p.gfix) return 0;
@@ -633,22 +545,15 @@ static std::atomic<int> g_op_plan_from{-1};
 // positions from which a call takes the plan path (0x7fffffff = never); ssg_set_operator_plan_threshold
 // (n <= 0: never)
 static int op_plan_from() {
-  int v = g_op_plan_from.load(std::memory_order_relaxed);
-  if (v < 0) {
-    v = env_int("SSG_OP_PLAN_FROM", OP_PLAN_FROM_DEFAULT);
-    if (v <= 0) v = 0x7fffffff;
-    g_op_plan_from.store(v, std::memory_order_relaxed);
-  }
-  return v;
+  return setting(g_op_plan_from, [] { const int v = env_int("SSG_OP_PLAN_FROM", OP_PLAN_FROM_DEFAULT); return v <= 0 ? 0x7fffffff : v; });
 }
 
 static hipMemPool_t op_pool() {
-  constexpr int MAXDEV = 64;
   static std::mutex mu;
   static hipMemPool_t tab[MAXDEV] = {};
   static bool failed[MAXDEV] = {};
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= MAXDEV) return nullptr;
+  const int dev = current_device_slot();
+  if (dev < 0) return nullptr;
   std::lock_guard<std::mutex> lk(mu);
   if (!tab[dev] && !failed[dev]) {
     hipMemPoolProps props{};
@@ -681,12 +586,9 @@ struct OpPlan {
 static bool op_wants_plan(int mc, int ks, int kw, int C, hipStream_t st, bool forward) {
   const long from = (long)op_plan_from() * (forward && op_plan_from() > 1 ? 3 : 1);
   if (from >= 0x7fffffffL || (long)mc < from || !dense_supported(ks, kw, C) || !dense_bwd_supported(ks, kw, C) || !grow_supported(ks, kw)) return false;
-  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-  if (hipStreamIsCapturing(st, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone) {
-    (void)hipGetLastError();
-    return false;
-  }
-  return true;
+  if (!stream_capturing(st)) return true;
+  (void)hipGetLastError();
+  return false;
 }
 
 // rank map, plan and duplicate list of `pos` (padded coordinates on a (Hp, Wp) image), everything relabelled to the
@@ -695,18 +597,13 @@ static int op_plan_build(const int *pos, int mc, int ks, int Hp, int Wp, size_t 
   hipMemPool_t pool = op_pool();
   if (!pool) return 0;
   const size_t npix = (size_t)Hp * Wp;
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    const size_t at = off;
-    off += align_up(bytes, 256);
-    return at;
-  };
-  const size_t o_mask = take(npix), o_edges = take(sizeof(int) * 3 * (size_t)mc), o_counts = take(sizeof(int) * 8),
-               o_rank = take(sizeof(int) * npix), o_plan = take(fwd_plan_bytes(1, Hp, Wp, mc)),
-               o_perm = take(sizeof(int) * (size_t)mc), o_dup = take(sizeof(int) * (size_t)mc), o_ndup = take(sizeof(int) * 4),
-               o_es = take(edge_scratch_bytes(1, Hp, Wp)), o_bs = take(bwd_scratch_bytes);
+  Carver c;
+  const size_t o_mask = c.take(npix), o_edges = c.take(sizeof(int) * 3 * (size_t)mc), o_counts = c.take(sizeof(int) * 8),
+               o_rank = c.take(sizeof(int) * npix), o_plan = c.take(fwd_plan_bytes(1, Hp, Wp, mc)),
+               o_perm = c.take(sizeof(int) * (size_t)mc), o_dup = c.take(sizeof(int) * (size_t)mc), o_ndup = c.take(sizeof(int) * 4),
+               o_es = c.take(edge_scratch_bytes(1, Hp, Wp)), o_bs = c.take(bwd_scratch_bytes);
   void *base = nullptr;
-  if (hipMallocFromPoolAsync(&base, off, pool, st) != hipSuccess || !base) {
+  if (hipMallocFromPoolAsync(&base, c.end, pool, st) != hipSuccess || !base) {
     (void)hipGetLastError();
     return 0;
   }
@@ -792,13 +689,14 @@ int ssg_compute_similarity(const float *image, const int *pos, float *out, int m
     if (!rc && o.base) {
       // dense tiles -> shared-term kernel in raw mode, the rest (the plan's tile order, caller's row numbers) -> the
       // direct kernels, duplicates of a position -> a direct launch of their own
+      const PlanView pv = plan_view(o.plan, 1, height, width);
       DenseParams d{};
       d.img[0] = image;
       d.out[0] = out;
       d.nimg = 1;
       d.rank = o.rank;
-      d.n_dense = o.plan + 1;
-      d.tiles = o.plan + 4;
+      d.n_dense = pv.dense_hdr;
+      d.tiles = pv.tiles;
       d.max_tiles = dense_max_tiles(1, height, width, psize);
       d.n_host = mc;
       d.B = 1;
@@ -812,8 +710,8 @@ int ssg_compute_similarity(const float *image, const int *pos, float *out, int m
       fork_side(sc);
       rc = launch_fwd_dense(d, psize, ksize, channel, sc.dense());
       FwdParams q = p;
-      q.order = o.plan + fwd_plan_order_offset(1, height, width);
-      q.n_dev = o.plan;   // n_sparse
+      q.order = pv.sparse_order;
+      q.n_dev = pv.n_sparse;
       if (!rc) rc = launch_fwd(q, sc.direct());
       const int rcj = join_side(sc);
       if (!rc) rc = rcj;
@@ -936,6 +834,7 @@ static int map_forward_impl(const float *img, const float *img2, int B, int C, i
   p.dbg = dbg_mask() & 0xff;
   if (fwd_plan && rank_map && dense_supported(ks, kw, C)) {
     // dense tiles -> shared-term kernel; the rest (plan's own tile-major order) -> direct kernels
+    const PlanView pv = plan_view(fwd_plan, B, H, W);
     DenseParams d{};
     d.img[0] = img;
     d.img[1] = img2;
@@ -943,8 +842,8 @@ static int map_forward_impl(const float *img, const float *img2, int B, int C, i
     d.out[1] = ssg2;
     d.nimg = p.nimg;
     d.rank = rank_map;
-    d.n_dense = fwd_plan + 1;
-    d.tiles = fwd_plan + 4;
+    d.n_dense = pv.dense_hdr;
+    d.tiles = pv.tiles;
     d.max_tiles = dense_max_tiles(B, H, W, ks);
     d.n_dev = n_edges_dev;
     d.n_host = n_rows;
@@ -962,7 +861,7 @@ static int map_forward_impl(const float *img, const float *img2, int B, int C, i
       d.tm[1] = tm->rows[1];
       d.tm_slots = tm->slots;
       d.max_strips = strips_enabled() ? dense_max_strips(B, H, W, ks) : 0;   // (k_s 49: whole strips of heavy tiles)
-      d.strips = d.max_strips ? fwd_plan + fwd_plan_strip_offset(B, H, W) : nullptr;
+      d.strips = d.max_strips ? pv.strips : nullptr;
     }
     if (row_scale && !row_scale_zeroed) {   // 0 = "this row is already normalised" (the rows of the direct kernels)
       const int rc0 = (int)hipMemsetAsync(row_scale, 0, sizeof(double) * 2 * (size_t)n_rows, sc.st);
@@ -970,8 +869,8 @@ static int map_forward_impl(const float *img, const float *img2, int B, int C, i
     }
     fork_side(sc, dbg_mask() & ((1 << 25) | (1 << 26)));   // (ssg_set_overlap)
     int rc = (dbg_mask() & (1 << 25)) ? 0 : launch_fwd_dense(d, ks, kw, C, sc.dense());
-    p.order = fwd_plan + fwd_plan_order_offset(B, H, W);
-    p.n_dev = fwd_plan;  // n_sparse
+    p.order = pv.sparse_order;
+    p.n_dev = pv.n_sparse;
     p.rows_hint = sc.rows_hint;
     if (!rc && !(dbg_mask() & (1 << 26))) rc = launch_fwd(p, sc.direct());
     if (sc.chains) return rc;   // two chains: the backward's kernels follow on the same two streams (the caller joins)
@@ -1032,7 +931,7 @@ int ssg_map_backward(const float *img, int B, int C, int H, int W, const int *ed
   return rc ? rc : det_end(p, (hipStream_t)stream);
 }
 
-size_t ssg_grad_fix_bytes(int B, int C, int H, int W) { return sizeof(long long) * ((size_t)B * C * H * W + 8); }
+size_t ssg_grad_fix_bytes(int B, int C, int H, int W) { return grad_fix_bytes(B, C, H, W); }
 
 static size_t partials_bytes(int B, int H, int W, int n_rows) {
   return align_up(2 * sizeof(float) * bwd_max_partials(B, H, W, n_rows) + 64, 256);
@@ -1121,49 +1020,35 @@ int ssg_loss_backward(const float *sr, int B, int C, int H, int W, const int *ed
   return rc ? rc : rcj;
 }
 
+// a capacity as the sizes below count it: room for one row at least
+static size_t rows_of(int capacity) { return (size_t)(capacity > 0 ? capacity : 1); }
 // two row-major regions (sr, gt); at k_s = 49 two tile-major regions of the same size behind them
-static size_t rows_region_bytes(int capacity, int ks) {
-  return align_up(sizeof(float) * (size_t)(capacity > 0 ? capacity : 1) * ks * ks, 256);
-}
+static size_t rows_region_bytes(int capacity, int ks) { return align_up(sizeof(float) * rows_of(capacity) * ks * ks, 256); }
 // (a tile-major region: capacity / 128 slots and a spare one for the short strips of ssg_fwd_strip)
 static size_t tm_region_bytes(int capacity, int ks) {
-  return align_up(sizeof(float) * ((size_t)(capacity > 0 ? capacity : 1) / TM_PX + 1) * ks * ks * TM_PX, 256);
+  return align_up(sizeof(float) * (rows_of(capacity) / TM_PX + 1) * ks * ks * TM_PX, 256);
 }
 size_t ssg_loss_tm_bytes(int capacity, int ks) { return ks == 49 ? 2 * tm_region_bytes(capacity, ks) : 0; }
 size_t ssg_loss_rows_bytes(int capacity, int ks) {
   return 2 * rows_region_bytes(capacity, ks) + ssg_loss_tm_bytes(capacity, ks);
 }
 
-size_t ssg_loss_workspace_bytes(int B, int H, int W, int capacity, int ks) {
-  return align_up(sizeof(int) * 3 * (size_t)(capacity > 0 ? capacity : 1), 256) +
-         align_up(2 * sizeof(double) * (size_t)(capacity > 0 ? capacity : 1), 256) +
-         align_up(sizeof(int) * (size_t)B * H * W, 256) + align_up(sizeof(int) * (size_t)(capacity > 0 ? capacity : 1), 256) +
-         align_up(fwd_plan_bytes(B, H, W, capacity), 256) + align_up(edge_scratch_bytes(B, H, W), 256) +
-         align_up(ssg_loss_scratch_bytes(B, H, W, capacity, ks), 256);
-}
-
-// carving of the fused call's workspace (one place: loss_fwd_bwd_impl and ssg_loss_workspace_layout use it)
+// carving of the fused call's workspace (one place: the size, loss_fwd_bwd_impl and ssg_loss_workspace_layout use it)
 struct LossWorkspace {
   size_t edges, rank, order, plan, escratch, lscratch, row_scale, base_bytes, rows[2], tm[2];
   int tm_slots;
 };
 static LossWorkspace carve_workspace(int B, int H, int W, int capacity, int ks, bool fused = true) {
   LossWorkspace w{};
-  size_t o = 0;
-  w.edges = o;
-  o += align_up(sizeof(int) * 3 * (size_t)capacity, 256);
-  w.rank = o;
-  o += align_up(sizeof(int) * (size_t)B * H * W, 256);
-  w.order = o;
-  o += align_up(sizeof(int) * (size_t)capacity, 256);
-  w.plan = o;
-  o += align_up(fwd_plan_bytes(B, H, W, capacity), 256);
-  w.escratch = o;
-  o += align_up(edge_scratch_bytes(B, H, W), 256);
-  w.lscratch = o;
-  o += align_up(ssg_loss_scratch_bytes(B, H, W, capacity, ks), 256);
-  w.row_scale = o;
-  w.base_bytes = ssg_loss_workspace_bytes(B, H, W, capacity, ks);
+  Carver c;
+  w.edges = c.take(sizeof(int) * 3 * rows_of(capacity));
+  w.rank = c.take(sizeof(int) * (size_t)B * H * W);
+  w.order = c.take(sizeof(int) * rows_of(capacity));
+  w.plan = c.take(fwd_plan_bytes(B, H, W, capacity));
+  w.escratch = c.take(edge_scratch_bytes(B, H, W));
+  w.lscratch = c.take(ssg_loss_scratch_bytes(B, H, W, capacity, ks));
+  w.row_scale = c.take(2 * sizeof(double) * rows_of(capacity));
+  w.base_bytes = c.end;
   const size_t region = rows_region_bytes(capacity, ks);
   w.rows[0] = w.base_bytes;
   w.rows[1] = w.rows[0] + region;
@@ -1174,6 +1059,10 @@ static LossWorkspace carve_workspace(int B, int H, int W, int capacity, int ks, 
   }
   if (!fused) w.rows[0] = w.rows[1] = 0;
   return w;
+}
+
+size_t ssg_loss_workspace_bytes(int B, int H, int W, int capacity, int ks) {
+  return carve_workspace(B, H, W, capacity, ks).base_bytes;
 }
 
 int ssg_loss_workspace_layout(int B, int H, int W, int capacity, int ks, int fused, size_t out[9]) {
@@ -1201,12 +1090,12 @@ static int loss_fwd_bwd_impl(const float *sr, const float *gt, const void *mask,
   if (mask_kind != 2 && !mask) return SSG_E_BADARG;
   // fused step (no SSG output): the rows are the engine's scratch, behind the regular workspace
   const bool fused = ssg_sr == nullptr;
-  const size_t base_bytes = ssg_loss_workspace_bytes(B, H, W, capacity, ks);
+  const LossWorkspace lw = carve_workspace(B, H, W, capacity, ks, fused);
+  const size_t base_bytes = lw.base_bytes;
   if (workspace_bytes < base_bytes + (fused ? ssg_loss_rows_bytes(capacity, ks) : 0)) return SSG_E_WORKSPACE;
   // the edge-list builder's first kernel clears the row scales, the fixed-point sums and (ssg_loss_step) the gradient
   // with 16-byte stores: offset views of a larger buffer must keep that alignment (include/ssg_hip.h)
   if ((((uintptr_t)workspace) | ((uintptr_t)grad_fix) | ((uintptr_t)grad_sr)) & 15) return SSG_E_ALIGN;
-  const LossWorkspace lw = carve_workspace(B, H, W, capacity, ks, fused);
   char *ws = (char *)workspace;
   TileMajor tm;
   if (fused) {
@@ -1233,7 +1122,7 @@ static int loss_fwd_bwd_impl(const float *sr, const float *gt, const void *mask,
     int *ticket = (int *)(ws + lw.escratch);
     int rc = launch_tiny_edge_list(mask_kind == 2 ? (const void *)gt : mask, mask_kind, mask_kind == 2 ? 3 : mask_channels, B, H, W,
                                    mask_stride, lap_threshold, edges, capacity, counts, rank, ticket, 16,
-                                   fixed ? grad_fix : nullptr, sizeof(long long) * ((size_t)B * C * H * W + 8),
+                                   fixed ? grad_fix : nullptr, grad_fix_bytes(B, C, H, W),
                                    (grad_is_output && grad_sr && !fixed) ? (void *)grad_sr : nullptr,
                                    sizeof(float) * (size_t)B * C * H * W, (hipStream_t)stream);
     if (rc) return rc;
@@ -1282,7 +1171,7 @@ static int loss_fwd_bwd_impl(const float *sr, const float *gt, const void *mask,
   // the schedule of the whole step, from the hint the builder below has not overwritten yet: two chains where there is a
   // gradient and the sizes have a dense / direct split
   Schedule sc = schedule((hipStream_t)stream, ks, defer && grad_sr);
-  const size_t fix_bytes = sizeof(long long) * ((size_t)B * C * H * W + 8), rs_bytes = 2 * sizeof(double) * (size_t)capacity;
+  const size_t fix_bytes = grad_fix_bytes(B, C, H, W), rs_bytes = 2 * sizeof(double) * (size_t)capacity;
   int rc = edge_list_impl(mask_kind == 2 ? (const void *)gt : mask, mask_kind, mask_kind == 2 ? 3 : mask_channels, B, H,
                           W, mask_stride, lap_threshold, ks, edges, capacity, counts, rank, order, plan, escratch,
                           defer ? (void *)row_scale : nullptr, rs_bytes, zero_fix ? grad_fix : nullptr, fix_bytes,

@@ -18,7 +18,7 @@
 // reference operator's backward), dL/dS + saved S (similarity_map autograd), or
 // S_sr/S_gt for the fused L1 + KL criteria, whose partial sums are also
 // produced here (L1Loss basic_loss.py:66, KLDistanceLoss basic_loss.py:281).
-#include "ssg_common.hpp"
+#include "ssg_host.hpp"
 
 namespace ssg {
 
@@ -861,7 +861,6 @@ static size_t bwd_lds_bytes(int C) {
                                   G::WG + G::JOBS * 4 + G::JOBS * 4 + G::JOBS * (C + 1) * G::KW * G::KW + 8);
 }
 
-unsigned bwd_grid(const BwdParams &p);
 constexpr unsigned BWD_MAIN_GROUPS = 20480, BWD_TAIL_GRID = 512;   // (multiples of 8: the XCD-contiguous group mapping)
 
 template <class G, int KHC>

@@ -29,7 +29,7 @@
 // pixel and the image band advances by one row.  Cost per (tile, offset): ~200 wave instructions
 // whatever the number of edge pixels, against ~19 k lane-instructions per edge pixel and offset row
 // in the direct kernel.
-#include "ssg_common.hpp"
+#include "ssg_host.hpp"
 
 namespace ssg {
 

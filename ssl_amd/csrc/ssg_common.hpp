@@ -109,7 +109,7 @@ __device__ __forceinline__ void pin_block(float (&v)[R][N]) {
 
 // `order` entries: bits 0..29 = row; bit 30 of the FIRST entry of every group of ORDER_GROUP
 // consecutive entries = "these jobs are one image's edge pixels within 8 rows x 16 columns".
-// Dense tile list of a forward plan: hdr = plan + 1 points at {n_heavy, tile rows, n_light}; the tiles with more than
+// Dense tile list of a forward plan: hdr = PlanView::dense_hdr points at {n_heavy, tile rows, n_light}; the tiles with more than
 // 64 edge pixels (two or more 64-lane chunks in the forward's edge stage, i.e. the longest workgroups) are appended
 // from the front of the `n_super` slots, the others from the back, and slot t walks the heavy ones first: longest jobs
 // first shortens the kernel's tail (list scheduling of ~2,000 workgroups on 512 slots: -12 % makespan in a model).
@@ -415,13 +415,13 @@ struct GrowParams {
                           // behind the fixed-point sums by grad_fix_reduce: no atomics on one address)
   int ngroups;            // groups of 4 rows (set by launch_grad_rows)
   int grid_cap;           // > 0: at most this many workgroups, each walking several groups
-  // a call with a tile-major region: plan + 1 (tm_active's header), the region's slots, and the plan's list of the
-  // rows that are not in a dense tile (plan[0] of them)
+  // a call with a tile-major region: PlanView::dense_hdr (tm_active's header), the region's slots, and the plan's list
+  // of the rows that are not in a dense tile (PlanView::sparse_order, *PlanView::n_sparse of them)
   const int *tm_hdr;
   int tm_slots;
   const int *sparse_order;
   // two-chain step (ssg_api.hip): 0 every row; 1 the rows with a non-zero row scale only (the dense-tile kernels' rows,
-  // un-normalised); 2 the rows of the plan's sparse list only (tm_hdr = plan + 1, sparse_order; the direct kernels' rows)
+  // un-normalised); 2 the rows of the plan's sparse list only (tm_hdr, sparse_order; the direct kernels' rows)
   int only;
   // nullable: the bound word behind the fixed-point sums -- the first workgroup writes the a-priori bound of |G| there
   // (GRAD_LOSS: 4 kfac (|w_l1| u_1 + |w_kl| u_2) / (n P), grad_fix_bound_kernel's) instead of every group's maximum
@@ -456,7 +456,7 @@ __device__ __forceinline__ int tm_pixel_col(int lane) { return lane & 31; }
 // order of the plan's tile list varies from run to run -- atomic appends -- so a per-slot split would not be
 // reproducible): when the tiles fit the region's slots and are at least 60 % full on average -- a tile-major row
 // costs 128 pixels' worth of traffic whatever the number of edge pixels in the tile.
-// hdr = plan + 1 (hdr[-1] = rows NOT in a dense tile), nrows = rows of the call.
+// hdr = PlanView::dense_hdr (hdr[-1] = rows NOT in a dense tile), nrows = rows of the call.
 __device__ __forceinline__ bool tm_active(const int *hdr, int tm_slots, int nrows) {
   const int nd = hdr[0] + hdr[2];
   return tm_slots > 0 && nd <= tm_slots && 5 * (nrows - hdr[-1]) >= 3 * TM_PX * nd;
@@ -467,8 +467,8 @@ struct TmRowsParams {
   const float *tm[2];        // e rows of sr / gt
   const double *row_scale;   // [2][n_host]; tile-major rows carry -1/(sum e + eps)
   const int *rank;           // (B,H,W)
-  const int *n_dense;        // plan + 1
-  const int *tiles;          // plan + 4
+  const int *n_dense;        // PlanView::dense_hdr
+  const int *tiles;          // PlanView::tiles
   int n_tiles;               // launch bound = min(dense_max_tiles, tm_slots)
   int tm_slots;              // slots of the tile-major region (tm_active)
   const int *n_dev;
@@ -482,6 +482,34 @@ struct TmRowsParams {
   float *partials;           // (n_tiles, 2) out: criteria sums per workgroup
   float *gmax_part;          // nullable (n_tiles) out: upper bound of |G| per workgroup
   const float *out[2];       // nullable: the call's SSG tensors (n, k_s^2) -- ssg_rows_tm_mat writes the normalised rows
+};
+
+// ssg_fwd_dense / ssg_fwd_strip (ssg_dense.hip)
+struct DenseParams {
+  const float *img[2];
+  float *out[2];
+  int nimg;
+  const int *rank;      // (B,H,W) row of every pixel, -1 if not an edge pixel
+  const int *n_dense;   // device count of dense tiles
+  const int *tiles;     // dense tile ids
+  int max_tiles;        // launch bound per image slot
+  const int *n_dev;     // rows computed at all (capacity clamp), nullable
+  int n_host;
+  int B, H, W;
+  float sigma, eps;
+  int generalization;
+  int dbg;  // profiling ablations: bit0 no stores, bit1 no edge stage, bit2 (strips) no E/H stage, bit3 no rescale, bit6 no main loop
+  double *row_scale;  // nullable [nimg][n_host]: deferred normalisation -- the rows stay e, 1/(sum e + eps) goes here
+  // tile-major scratch rows (fused step at k_s = 49, ssg_api.hip; tm_active() in ssg_common.hpp decides per call):
+  // the tile in plan slot t leaves its e values at tm[img] + t * P * 128 + q * 128 + (64 ck + lane) -- every wave
+  // store is one aligned 256-byte run -- and marks its rows with a NEGATIVE row scale; nullptr / 0 = row-major rows only
+  float *tm[2];
+  int tm_slots;
+  int grid_tiles;  // plan slots this launch covers (per image)
+  const int *strips;  // k_s 49 tile-major calls: [0] number of strips, then (strip id, first slot) pairs; nullable
+  int max_strips;     // launch bound per image
+  int *status;        // nullable: library-owned device status word (ssg_device_status): bit 0 = plan of another tile height
+  int raw;            // 1: the reference operator's output -- out[n, q] += D[n, q] (similarity.cu:49), no epilogue
 };
 
 // ssg_bwd_dense (ssg_bwd_dense.hip)

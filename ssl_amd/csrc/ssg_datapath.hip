@@ -16,7 +16,7 @@
 //                      reference convolves with the 51 x 51 outer product; here the two blurs are separable row /
 //                      column passes through LDS tiles (2 x 51 instead of 2601 taps per pixel), the elementwise steps
 //                      ride in the column passes' epilogues: four launches, ~12 floats of HBM traffic per element.
-#include "ssg_common.hpp"
+#include "ssg_host.hpp"
 
 namespace ssg {
 

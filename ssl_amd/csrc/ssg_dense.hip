@@ -38,7 +38,7 @@
 // buffering) instead of the caller's row-major rows, and ssg_fwd_strip, which computes the forward rows of whole strips
 // of nine heavy tiles at once for tile-major calls (E/H shared by 36 centre rows).  ssg_common.hpp (TM_PX, tm_active,
 // TmRowsParams) and DESIGN.md sections 3-5 describe the layout and who reads it.
-#include "ssg_common.hpp"
+#include "ssg_host.hpp"
 
 namespace ssg {
 
@@ -95,33 +95,6 @@ __device__ __forceinline__ float tap_sum(const float (&v)[KW], const float (&w)[
   const f2 r2 = a + b;
   return (r2.x + r2.y) + __builtin_fmaf(w[KW - 1], v[KW - 1], rest);
 }
-
-struct DenseParams {
-  const float *img[2];
-  float *out[2];
-  int nimg;
-  const int *rank;      // (B,H,W) row of every pixel, -1 if not an edge pixel
-  const int *n_dense;   // device count of dense tiles
-  const int *tiles;     // dense tile ids
-  int max_tiles;        // launch bound per image slot
-  const int *n_dev;     // rows computed at all (capacity clamp), nullable
-  int n_host;
-  int B, H, W;
-  float sigma, eps;
-  int generalization;
-  int dbg;  // profiling ablations: bit0 no stores, bit1 no edge stage, bit2 (strips) no E/H stage, bit3 no rescale, bit6 no main loop
-  double *row_scale;  // nullable [nimg][n_host]: deferred normalisation -- the rows stay e, 1/(sum e + eps) goes here
-  // tile-major scratch rows (fused step at k_s = 49, ssg_api.hip; tm_active() in ssg_common.hpp decides per call):
-  // the tile in plan slot t leaves its e values at tm[img] + t * P * 128 + q * 128 + (64 ck + lane) -- every wave
-  // store is one aligned 256-byte run -- and marks its rows with a NEGATIVE row scale; nullptr / 0 = row-major rows only
-  float *tm[2];
-  int tm_slots;
-  int grid_tiles;  // plan slots this launch covers (per image)
-  const int *strips;  // k_s 49 tile-major calls: [0] number of strips, then (strip id, first slot) pairs; nullable
-  int max_strips;     // launch bound per image
-  int *status;        // nullable: library-owned device status word (ssg_device_status): bit 0 = plan of another tile height
-  int raw;            // 1: the reference operator's output -- out[n, q] += D[n, q] (similarity.cu:49), no epilogue
-};
 
 constexpr int DT_X = 32;  // centre columns per tile; rows: DT_Y = 16 - (k_w - 1) (8 for k_w = 9, 4 for k_w = 13)
 // Pixels of a U-row per lane: the 4 lanes of a quad cover the row without overlap (10 x 4 = 40 = U for k_w 9; 12 x 4

@@ -9,7 +9,7 @@
 // order-preserving scatter, then the tile order / plan kernels on the rank map (7-12 launches; k_s 49 plans with their
 // strips, callers that want the full order AND a plan).  The BANDED one (further down; every other call): 8-row x
 // 256-column blocks give the row-segment counts and the tile counts in one pass -- three launches.
-#include "ssg_common.hpp"
+#include "ssg_host.hpp"
 
 namespace ssg {
 
@@ -919,8 +919,6 @@ size_t edge_scratch_bytes(int B, int H, int W) {
   return chunked > banded ? chunked : banded;
 }
 
-int *plan_hint_device_word(hipStream_t st);   // ssg_api.hip: host-mapped {rows for the direct kernels, dense tiles} of the device's last plan
-
 static bool banded_enabled() {
   static const bool on = env_int("SSG_EDGE_BANDED", 1) != 0;   // (profiling build only: the chunked builder for every call)
   return on;
@@ -931,8 +929,15 @@ static size_t n_strips(int B, int H, int W) { return (size_t)B * ((H + STRIP_ROW
 // forward plan: [0] n_sparse, [1] n_heavy, [2] tile rows, [3] n_light, [4, 4+ns) the dense kernels' super-tile ids (heavy from the front, light from the back; ns =
 // n_super_tiles), then the k_s 49 forward's strip list (count, then n_strips (strip id, first place) pairs), then
 // (capacity) the tile-major order of the rows left to the direct kernels
-int fwd_plan_strip_offset(int B, int H, int W) { return 4 + (int)n_super_tiles(B, H, W); }
+constexpr int PLAN_HDR_WORDS = 4;
+int fwd_plan_strip_offset(int B, int H, int W) { return PLAN_HDR_WORDS + (int)n_super_tiles(B, H, W); }
 int fwd_plan_order_offset(int B, int H, int W) { return fwd_plan_strip_offset(B, H, W) + 1 + 2 * (int)n_strips(B, H, W); }
+PlanView plan_view(const int *plan, int B, int H, int W) {
+  return PlanView{plan, plan + 1, plan + PLAN_HDR_WORDS, plan + fwd_plan_strip_offset(B, H, W),
+                  plan + fwd_plan_order_offset(B, H, W)};
+}
+// (the builder below is the plan's one writer: the same places, writable)
+static int *plan_part(const int *part) { return const_cast<int *>(part); }
 
 size_t fwd_plan_bytes(int B, int H, int W, int capacity) {
   return sizeof(int) * ((size_t)fwd_plan_order_offset(B, H, W) + (size_t)(capacity > 0 ? capacity : 1));
@@ -963,7 +968,7 @@ int launch_edge_list(const void *mask, int kind, int mask_channels, int B, int H
     uint8_t *bits = (uint8_t *)(dflag + n_super_tiles(B, H, W)) + 64;
     const ZeroRanges z{{zero_a, zero_b, zero_c}, {zero_a ? zero_a_bytes : 0, zero_b ? zero_b_bytes : 0, zero_c ? zero_c_bytes : 0}};
     const unsigned grid = (unsigned)(B * ty_n * nseg);
-    int *order_out = plan ? plan + fwd_plan_order_offset(B, H, W) : order;
+    int *order_out = plan ? plan_part(plan_view(plan, B, H, W).sparse_order) : order;
     hipLaunchKernelGGL(band_count, dim3(grid), dim3(256), 0, st, p, nseg, segcnt, tcnt, bits, z);
     hipLaunchKernelGGL(band_scan, dim3(1), dim3(1024), 0, st, B, H, W, nseg, segcnt, segoff, counts, capacity, bits, tcnt, toff,
                        dense_thr, plan ? dflag : nullptr, plan, plan ? plan_hint_device_word(st) : nullptr);
@@ -986,19 +991,19 @@ int launch_edge_list(const void *mask, int kind, int mask_channels, int B, int H
   if (plan) {
     const int sty = plan_tile_rows;
     const int ns = B * ((H + sty - 1) / sty) * ((W + 31) / 32);
-    int *dflag = toff + nt, *order2 = plan + fwd_plan_order_offset(B, H, W);
-    int *strips = plan + fwd_plan_strip_offset(B, H, W);
+    const PlanView pv = plan_view(plan, B, H, W);
+    int *dflag = toff + nt, *tiles = plan_part(pv.tiles), *strips = plan_part(pv.strips), *order2 = plan_part(pv.sparse_order);
     if (sty == OT) {   // 8-row super-tiles = four order tiles each: counts are already there
       hipLaunchKernelGGL(plan_from_tile_counts, dim3((ns + 255) / 256), dim3(256), 0, st, B, H, W, dense_thr, dflag, plan,
-                         plan + 4, tcnt);
+                         tiles, tcnt);
     } else {
       const bool with_strips = sty == 4;
       hipLaunchKernelGGL(plan_count, dim3((ns + 3) / 4), dim3(256), 0, st, rank, B, H, W, sty, dense_thr, dflag, plan,
-                         plan + 4, nullptr, with_strips ? strips : nullptr);
+                         tiles, nullptr, with_strips ? strips : nullptr);
       if (with_strips) {
         const int nstr = (int)n_strips(B, H, W);
-        hipLaunchKernelGGL(strip_select, dim3((nstr + 255) / 256), dim3(256), 0, st, B, H, W, dflag, plan, plan + 4, strips);
-        hipLaunchKernelGGL(plan_append, dim3((ns + 255) / 256), dim3(256), 0, st, ns, dflag, plan, plan + 4);
+        hipLaunchKernelGGL(strip_select, dim3((nstr + 255) / 256), dim3(256), 0, st, B, H, W, dflag, plan, tiles, strips);
+        hipLaunchKernelGGL(plan_append, dim3((ns + 255) / 256), dim3(256), 0, st, ns, dflag, plan, tiles);
       }
       hipLaunchKernelGGL(tile_count_sparse, dim3((nt + 3) / 4), dim3(256), 0, st, rank, B, H, W, nt, sty, dflag, tcnt);
     }

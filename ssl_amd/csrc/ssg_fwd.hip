@@ -16,7 +16,7 @@
 // ssg_fwd_generic: any odd (k_s, k_w) at run time, one workgroup per job, one
 //   search offset per lane-iteration.  Correct, not fast; keeps unusual sizes on
 //   the GPU (there is no CPU fallback anywhere in the product path).
-#include "ssg_common.hpp"
+#include "ssg_host.hpp"
 
 namespace ssg {
 

@@ -17,7 +17,7 @@
 // Rows that live in the tile-major region of a k_s = 49 call (negative row scale) are not touched by ssg_grad_rows:
 // ssg_rows_tm (fused step) / ssg_rows_tm_mat (materialising call: it also writes the normalised SSG rows) below walk
 // them with lanes = pixels, and the dense backward forms their G itself.
-#include "ssg_common.hpp"
+#include "ssg_host.hpp"
 
 namespace ssg {
 

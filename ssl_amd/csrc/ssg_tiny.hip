@@ -24,7 +24,7 @@
 // cases; bit-reproducible in deterministic mode).  Taken by
 // ssg_loss_fwd_bwd / ssg_loss_step when B H W <= 16,384 pixels and capacity <= 4,096 rows (ssg_api.hip); ssg_set_tiny_step(0)
 // turns it off.
-#include "ssg_common.hpp"
+#include "ssg_host.hpp"
 
 namespace ssg {
 

@@ -310,6 +310,41 @@ def test_workspace_layout_of_the_fused_call():
     assert L.ssg_loss_workspace_layout(1, 64, 64, 0, 25, 1, lay) == -1 and L.ssg_loss_workspace_layout(1, 64, 64, 10, 25, 1, None) == -1
 
 
+def test_host_sizes_match_the_recorded_fixture():
+    """Fixture F21 (tests/golden/make_golden_sizes.py): every size the ABI reports and the nine words of
+    ssg_loss_workspace_layout, fused and not, over batch sizes, image sizes on and off the tile edges, the three kernel
+    sizes and capacities around the 128-pixel slot of the tile-major regions -- EXACTLY as recorded before the workspace
+    arithmetic was gathered into one carving.  Callers size their buffers with these numbers and the kernels index by
+    the offsets: neither may move unnoticed."""
+    import importlib.util
+    import json
+    from ssl_amd import _lib
+    spec = importlib.util.spec_from_file_location("make_golden_sizes", os.path.join(ROOT, "tests", "golden", "make_golden_sizes.py"))
+    gen = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(gen)
+    fix = json.load(open(os.path.join(ROOT, "tests", "golden", "f21_host_sizes.json")))
+    L = _lib.lib()
+    assert fix["abi_version"] == L.ssg_abi_version() and fix["channels"] == gen.CHANNELS
+    assert fix["columns"] == ["B", "H", "W", "ks", "capacity"] + list(gen.COLUMNS)
+    cases = list(gen.cases())
+    assert [tuple(r[:5]) for r in fix["rows"]] == cases and len(cases) == 3 * 5 * 3 * 7
+    for row in fix["rows"]:
+        assert gen.measure(L, *row[:5]) == row[5:], row[:5]
+
+
+def test_host_header_stands_alone(tmp_path):
+    """ssg_host.hpp -- the one declaration of every host function that crosses a file boundary -- compiles on its own
+    with -Wall -Werror, in the product and the profiling configuration (no kernel, a second or two)."""
+    from ssl_amd import _lib
+    tu = tmp_path / "host_header_only.hip"
+    tu.write_text('#include "ssg_host.hpp"\n')
+    for define in ([], ["-DSSG_PROFILE"]):
+        cmd = [os.environ.get("HIPCC", "/opt/rocm/bin/hipcc"), "-std=c++17", "--offload-arch=gfx950", "-Wall", "-Werror", "-I", _lib.CSRC] + define + \
+              ["-c", str(tu), "-o", str(tmp_path / "host_header_only.o")]
+        out = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+        assert out.returncode == 0, out.stdout
+
+
 def test_plan_built_for_another_tile_height_is_refused():
     """A dense/direct plan is cut for one tile height (8 rows for k_s <= 25, 4 for k_s = 49) and records the k_s it
     was built for; handing it to a call with the other geometry raises before anything is launched (the dense
