@@ -291,13 +291,6 @@ static int *device_status_word() {
 
 static bool sizes_ok(int ks, int kw) { return ks > 0 && kw > 0 && (ks & 1) && (kw & 1) && kw <= ks; }
 
-static size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
-// lays the pieces of a buffer out one behind the other, each on a 256-byte boundary
-struct Carver {
-  size_t end = 0;
-  size_t take(size_t bytes) { return std::exchange(end, end + align_up(bytes, 256)); }
-};
-
 // Waves per tile of the dense-tile backward (each takes a contiguous range of offset rows): by default chosen on the
 // device so that the launch fills the chip about once; SSG_BWD_QSPLIT fixes it in the profiling build (experiments).
 static int bwd_qsplit() {   // 0 = chosen on the device from the number of dense tiles (DenseBwdParams::qsplit)

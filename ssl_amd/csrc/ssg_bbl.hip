@@ -32,18 +32,17 @@
 // two-pass unbiased variance, the threshold at the store (the layout of ssg_ldl.hip's ldl_map).
 // Compiled with -ffp-contract=off (csrc/Makefile): the luminance (0.2989 r + 0.587 g) + 0.114 b is rounded product by
 // product like the reference's torch expression.
-#include "../../include/ssg_hip.h"
-
 #include <math.h>
 
-#include "ssg_common.hpp"
+#include "ssg_pixel.hpp"
 
 namespace ssg {
 namespace bbl {
 
+using namespace pixel;             // NT, sgnf, block_sum, the flat mask's 32 x 16 tile and its reflect halo
+
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
-constexpr int NT = 256;            // threads per workgroup, every kernel
 constexpr int BLK = 32;            // rows / candidates per operand block (the MFMA tile side)
 constexpr int KP = 32;             // padded K of a stored block: BLK * KP floats = 4 KiB
 constexpr int DMAX = KP - 1;       // d + 1 <= KP
@@ -69,8 +68,6 @@ struct Args {
   int H4, W4, nw4, N4;  // level 1/4
   int M, nrb, ncb, nsplit, cbs, nb3;
 };
-
-__device__ __forceinline__ float sgnf(float x) { return (float)((x > 0.f) - (x < 0.f)); }
 
 // one sample of the bicubic 1/2 (sh = 1) or 1/4 (sh = 2) level of an H x W plane
 __device__ __forceinline__ float level_sample(const float *p, int H, int W, int sh, int y, int x) {
@@ -218,16 +215,6 @@ __global__ __launch_bounds__(NT) void bbl_search(Args a) {
   }
 }
 
-// fixed-order workgroup sum of one fp64 value (every thread must call it; thread 0's result is the sum)
-__device__ __forceinline__ double block_sum(double v, double *sh) {
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off);
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-  __syncthreads();
-  double s = sh[0];
-  for (int i = 1; i < NT / 64; ++i) s += sh[i];
-  return s;
-}
-
 // ------------------------------------------------------------------------------------- gather, loss and gradient ---
 __global__ __launch_bounds__(NT) void bbl_loss(Args a) {
   __shared__ double sh[NT / 64];
@@ -280,19 +267,6 @@ __global__ __launch_bounds__(NT) void bbl_fold(Args a) {
 }
 
 // ----------------------------------------------------------------------------------------------------- flat mask ---
-constexpr int TW = 32, TH = 16;          // output tile: 2 pixels per thread
-constexpr int KMAX = 15, RMAX = KMAX / 2;
-constexpr int LH = TH + 2 * RMAX;        // 30 tile rows with the largest halo
-constexpr int LW = TW + 2 * RMAX + 1;    // 47: row stride (+1 breaks the power-of-two stride)
-
-// reflect (pad < n) and clamp: coordinates beyond the padded range only occur in tile rows / columns that lie outside
-// the image and are never used; the clamp keeps their loads in bounds
-__device__ __forceinline__ int reflect_clamp(int i, int n) {
-  i = i < 0 ? -i : i;
-  i = i >= n ? 2 * n - 2 - i : i;
-  return min(max(i, 0), n - 1);
-}
-
 template <int KT>
 __global__ __launch_bounds__(NT) void flat_mask(const float *img, float *mask, int H, int W, int k, float thresh,
                                                 int tiles_x) {
@@ -301,12 +275,7 @@ __global__ __launch_bounds__(NT) void flat_mask(const float *img, float *mask, i
   const int b = blockIdx.y, HW = H * W;
   const int tx0 = (blockIdx.x % tiles_x) * TW, ty0 = (blockIdx.x / tiles_x) * TH;
   const float *r = img + (size_t)b * 3 * HW, *g = r + HW, *bl = g + HW;
-  const int lw = TW + 2 * R, lh = TH + 2 * R;
-  for (int i = threadIdx.x; i < lh * lw; i += NT) {
-    const int ly = i / lw, lx = i - ly * lw;
-    const int at = reflect_clamp(ty0 - R + ly, H) * W + reflect_clamp(tx0 - R + lx, W);
-    sl[ly][lx] = (0.2989f * r[at] + 0.587f * g[at]) + 0.114f * bl[at];
-  }
+  load_halo_tile(sl, ty0, tx0, R, H, W, [&](int at) { return (0.2989f * r[at] + 0.587f * g[at]) + 0.114f * bl[at]; });
   __syncthreads();
   const float inv_n = 1.f / (float)(K * K), inv_n1 = 1.f / (float)(K * K - 1);
   const int lx = threadIdx.x & (TW - 1);
@@ -332,8 +301,6 @@ __global__ __launch_bounds__(NT) void flat_mask(const float *img, float *mask, i
 struct Layout {
   size_t QT, CT, pmin, pidx, part, total;
 };
-
-inline size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 // geometry of a call: everything in Args but the pointers and weights
 inline void geometry(Args &a, int B, int C, int H, int W, int k, int s) {
@@ -361,12 +328,13 @@ inline void geometry(Args &a, int B, int C, int H, int W, int k, int s) {
 inline Layout layout(const Args &a) {
   Layout L;
   const size_t blk = sizeof(float) * KP * BLK;
-  L.QT = 0;
-  L.CT = up256(L.QT + blk * a.B * a.nrb);
-  L.pmin = up256(L.CT + blk * a.B * a.ncb);
-  L.pidx = up256(L.pmin + sizeof(float) * (size_t)a.B * a.nsplit * a.nrb * BLK);
-  L.part = up256(L.pidx + sizeof(int) * (size_t)a.B * a.nsplit * a.nrb * BLK);
-  L.total = up256(L.part + sizeof(double) * (size_t)a.B * a.nb3);
+  Carver c;
+  L.QT = c.take(blk * a.B * a.nrb);
+  L.CT = c.take(blk * a.B * a.ncb);
+  L.pmin = c.take(sizeof(float) * (size_t)a.B * a.nsplit * a.nrb * BLK);
+  L.pidx = c.take(sizeof(int) * (size_t)a.B * a.nsplit * a.nrb * BLK);
+  L.part = c.take(sizeof(double) * (size_t)a.B * a.nb3);
+  L.total = c.end;
   return L;
 }
 
@@ -385,8 +353,8 @@ inline int prepare(Args &a, const float *x, const float *g, int B, int C, int H,
   if (rc) return rc;
   geometry(a, B, C, H, W, k, s);
   const Layout L = layout(a);
-  if (ws_bytes < L.total) return SSG_E_WORKSPACE;
-  if ((uintptr_t)ws & 15) return SSG_E_ALIGN;
+  const int ws_rc = check_workspace(ws, ws_bytes, L.total);
+  if (ws_rc) return ws_rc;
   char *base = (char *)ws;
   a.x = x;
   a.g = g;

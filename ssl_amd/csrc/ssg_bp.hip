@@ -24,16 +24,18 @@
 //   bp_bwd<S>  a 64 x 32 gradient tile per workgroup: the <= 20 x 12 (s = 4) upstream values its pixels' copies touch
 //              are loaded into LDS (the arrays are one longer per side: 21 x 13), the column gather runs LDS -> LDS, the row gather LDS -> global.  Workgroup 0 also
 //              folds the forward's partials, in index order, into the loss.
-#include "../../include/ssg_hip.h"
-
 #include <math.h>
 
-#include "ssg_common.hpp"
+#include "ssg_pixel.hpp"
 
 namespace ssg {
 namespace bp {
 
-constexpr int NT = 256;        // threads per workgroup, every kernel
+using pixel::NT;               // (by name: this file has a KMAX of its own, the longest tap row)
+using pixel::block_sum;
+using pixel::check_workspace;
+using pixel::sgnf;
+
 constexpr int OTW = 16;        // forward: output tile
 constexpr int OTH = 8;
 constexpr int GW = 64;         // backward: gradient tile
@@ -60,24 +62,12 @@ struct Args {
   int btx, bty;                // backward tiles
 };
 
-__device__ __forceinline__ float sgnf(float x) { return (float)((x > 0.f) - (x < 0.f)); }
-
 // symmetric padding: -1-i -> i, n+i -> n-1-i.  Coordinates beyond the padded range only occur in tile rows / columns
 // that no output of the image uses; the clamp keeps their loads in bounds.
 __device__ __forceinline__ int sym_clamp(int i, int n) {
   i = i < 0 ? -1 - i : i;
   i = i >= n ? 2 * n - 1 - i : i;
   return min(max(i, 0), n - 1);
-}
-
-// fixed-order workgroup sum of one fp64 value (every thread must call it; thread 0's result is the sum)
-__device__ __forceinline__ double block_sum(double v, double *sh) {
-  for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off);
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-  __syncthreads();
-  double s = sh[0];
-  for (int i = 1; i < NT / 64; ++i) s += sh[i];
-  return s;
 }
 
 // ------------------------------------------------------------------------------------------------------ forward ---
@@ -212,8 +202,6 @@ __global__ __launch_bounds__(NT) void bp_bwd(Args a) {
 }
 
 // ---------------------------------------------------------------------------------------------------------- host ---
-inline size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 inline double keys(double r) {
   const double a = -0.5, x = fabs(r);
   if (x <= 1.0) return (a + 2) * x * x * x - (a + 3) * x * x + 1;
@@ -249,9 +237,10 @@ struct Layout {
 
 inline Layout layout(const Args &a) {
   Layout L;
-  L.sg = 0;
-  L.part = up256(sizeof(float) * (size_t)a.P * a.ho * a.wo);
-  L.total = up256(L.part + sizeof(double) * (size_t)a.fwg);
+  Carver c;
+  L.sg = c.take(sizeof(float) * (size_t)a.P * a.ho * a.wo);
+  L.part = c.take(sizeof(double) * (size_t)a.fwg);
+  L.total = c.end;
   return L;
 }
 
@@ -324,8 +313,8 @@ int ssg_bp_loss(const float *x, const float *lq, int planes, int H, int W, int s
   Args a{};
   geometry(a, planes, H, W, s);
   const Layout L = layout(a);
-  if (workspace_bytes < L.total) return SSG_E_WORKSPACE;
-  if ((uintptr_t)workspace & 15) return SSG_E_ALIGN;
+  const int ws_rc = check_workspace(workspace, workspace_bytes, L.total);
+  if (ws_rc) return ws_rc;
   a.x = x;
   a.lq = lq;
   a.y = y_out;

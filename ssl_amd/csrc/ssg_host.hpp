@@ -7,6 +7,14 @@
 
 namespace ssg {
 
+// ---- every workspace and scratch buffer of the library ----
+inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+// lays the pieces of a buffer out one behind the other, each on a 256-byte boundary
+struct Carver {
+  size_t end = 0;
+  size_t take(size_t bytes) { return std::exchange(end, end + align_up(bytes, 256)); }
+};
+
 // ---- ssg_fwd.hip: direct forward ----
 int launch_fwd(const FwdParams &p, hipStream_t st);
 const char *fwd_kernel_name(int ks, int kw);

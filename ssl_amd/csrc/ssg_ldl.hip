@@ -36,19 +36,14 @@
 // Conditioning (measured against an fp64 evaluation, profiles/ldl_fp64_parity.txt): w, loss and gradient stay within
 // about 1e-6 of their maximum in the callers' regime and within 5e-6 at mean(r) / std(r) = 30; the gather's
 // r_q sum G - sum G mu loses digits in proportion to that ratio and crosses 1e-5 near 100 (4e-5 at 300 to 500).
-#include "../../include/ssg_hip.h"
-
-#include "ssg_common.hpp"
+#include "ssg_pixel.hpp"
 
 namespace ssg {
 namespace ldl {
 
-constexpr int NT = 256;                  // threads per workgroup, every kernel
+using namespace pixel;                   // NT, sgnf, the 32 x 16 tile of ldl_map / ldl_grad and its reflect halo
+
 constexpr int RES_PX = 4;                // pixels per thread in ldl_residual
-constexpr int TW = 32, TH = 16;          // output tile of ldl_map / ldl_grad: 2 pixels per thread
-constexpr int KMAX = 15, RMAX = KMAX / 2;
-constexpr int LH = TH + 2 * RMAX;        // 30 tile rows with the largest halo
-constexpr int LW = TW + 2 * RMAX + 1;    // 47: row stride of the haloed tiles (+1 breaks the power-of-two stride)
 
 enum Mode : int { LOSS = 0, MAP = 1, LOCALVAR = 2 };
 
@@ -68,21 +63,11 @@ struct Args {
   int B, C, H, W, k, nb1, tiles_x, ntile;
 };
 
-__device__ __forceinline__ float sgnf(float x) { return (float)((x > 0.f) - (x < 0.f)); }
-
 // r = sum_c |g - o| in channel order (torch.sum over dim 1 of small C accumulates c = 0, 1, ... in turn)
 __device__ __forceinline__ float resid(const float *o, const float *g, size_t at, int C, int HW) {
   float r = fabsf(g[at] - o[at]);
   for (int c = 1; c < C; ++c) r += fabsf(g[at + (size_t)c * HW] - o[at + (size_t)c * HW]);
   return r;
-}
-
-// reflect (pad < n) and clamp: coordinates beyond the padded range only occur in tile rows / columns that lie outside
-// the image and are never used; the clamp keeps their loads in bounds
-__device__ __forceinline__ int reflect_clamp(int i, int n) {
-  i = i < 0 ? -i : i;
-  i = i >= n ? 2 * n - 2 - i : i;
-  return min(max(i, 0), n - 1);
 }
 
 // how often source sample p (0 <= p < n) sits in the window of radius R around q under reflect padding:
@@ -91,7 +76,8 @@ __device__ __forceinline__ int mult(int q, int p, int n, int R) {
   return (abs(q - p) <= R) + (q != 0 && p + q <= R) + (q != n - 1 && 2 * (n - 1) - q - p <= R);
 }
 
-// fixed-order workgroup sum of two fp64 values (every thread gets the result; every thread must call it)
+// fixed-order workgroup sum of two fp64 values (every thread gets the result; every thread must call it).  Not
+// pixel::block_sum twice: it opens with a barrier because image_stats calls it back to back on one buffer.
 __device__ __forceinline__ double2 block_sum2(double a, double b, double2 *sh) {
   __syncthreads();   // sh may still be read by a previous call
   for (int off = 32; off > 0; off >>= 1) {
@@ -170,12 +156,7 @@ __global__ __launch_bounds__(NT) void ldl_map(Args a) {
   const int b = blockIdx.y, HW = a.H * a.W;
   const int tx0 = (blockIdx.x % a.tiles_x) * TW, ty0 = (blockIdx.x / a.tiles_x) * TH;
   const float *rs = a.rsrc + (size_t)b * HW;
-  const int lw = TW + 2 * R, lh = TH + 2 * R;
-  for (int i = threadIdx.x; i < lh * lw; i += NT) {
-    const int ly = i / lw, lx = i - ly * lw;
-    const float v = rs[reflect_clamp(ty0 - R + ly, a.H) * a.W + reflect_clamp(tx0 - R + lx, a.W)];
-    sr[ly][lx] = MODE == LOCALVAR ? v : fabsf(v);
-  }
+  load_halo_tile(sr, ty0, tx0, R, a.H, a.W, [&](int at) { return MODE == LOCALVAR ? rs[at] : fabsf(rs[at]); });
   __syncthreads();
   const float P = MODE == LOCALVAR ? 1.f : image_stats(a, b, false, sh).P;   // (its block sums end in a barrier)
   const float inv_n = 1.f / (float)(K * K), inv_n1 = 1.f / (float)(K * K - 1);
@@ -325,21 +306,20 @@ struct Layout {
   int nb1, tiles_x, ntile;
 };
 
-inline size_t up256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 inline Layout layout(int B, int H, int W) {
   Layout L;
   const size_t n = (size_t)B * H * W;
   L.nb1 = (H * W + NT * RES_PX - 1) / (NT * RES_PX);
   L.tiles_x = (W + TW - 1) / TW;
   L.ntile = L.tiles_x * ((H + TH - 1) / TH);
-  L.rs = 0;
-  L.w = up256(L.rs + 4 * n);
-  L.G = up256(L.w + 4 * n);
-  L.GM = up256(L.G + 4 * n);
-  L.p1 = up256(L.GM + 4 * n);
-  L.p2 = up256(L.p1 + sizeof(double2) * (size_t)B * L.nb1);
-  L.total = up256(L.p2 + sizeof(double2) * (size_t)B * L.ntile);
+  Carver c;
+  L.rs = c.take(4 * n);
+  L.w = c.take(4 * n);
+  L.G = c.take(4 * n);
+  L.GM = c.take(4 * n);
+  L.p1 = c.take(sizeof(double2) * (size_t)B * L.nb1);
+  L.p2 = c.take(sizeof(double2) * (size_t)B * L.ntile);
+  L.total = c.end;
   return L;
 }
 
@@ -348,9 +328,7 @@ inline int check(int B, int C, int H, int W, int k, const void *ws, size_t ws_by
   if (k < 3 || k % 2 == 0 || B <= 0 || C <= 0 || H <= 0 || W <= 0) return SSG_E_BADARG;
   if (k > KMAX) return SSG_E_TOOLARGE;
   if (H <= k / 2 || W <= k / 2) return SSG_E_IMAGESMALL;
-  if (ws_bytes < layout(B, H, W).total) return SSG_E_WORKSPACE;
-  if ((uintptr_t)ws & 15) return SSG_E_ALIGN;   // the partials are read as 16-byte pairs
-  return 0;
+  return check_workspace(ws, ws_bytes, layout(B, H, W).total);
 }
 
 inline Args make_args(const float *o, const float *g, const float *e, int B, int C, int H, int W, int k, void *ws,

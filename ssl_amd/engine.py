@@ -30,6 +30,36 @@ def _f32c(t):
     return t.detach().to(torch.float32).contiguous()
 
 
+def _launch(dev, fn, *args):
+    """One call of the C ABI on the GPU that holds the call's tensors (whatever the current device is), on torch's
+    current stream of that GPU -- the last argument of every launching entry point."""
+    with torch.cuda.device(dev):
+        _lib.check(fn(*args, _stream()))
+
+
+def _workspace(nbytes, dev):
+    """(buffer, nbytes) for a size the library reported: at least one byte, so that the pointer is never NULL."""
+    return torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev), nbytes
+
+
+def _mask_kind(mask, image_channels):
+    """(mask as the C ABI reads it, kind): uint8 / bool -> kind 1 (edge pixel <=> value 1 (True), like `mask == 1`),
+    float -> kind 0, None -> kind 2, the Laplacian mask of the call's GT, which must have 3 channels."""
+    if mask is None:
+        if image_channels != 3:
+            raise ValueError("Laplacian edge mask needs a 3-channel image")
+        return None, 2
+    if mask.dtype == torch.uint8 or mask.dtype == torch.bool:
+        return mask.contiguous().view(torch.uint8), 1
+    return _f32c(mask), 0
+
+
+def _reduction_is_mean(name, reduction):
+    if reduction not in ('mean', 'sum'):
+        raise ValueError(f"ssl_amd: {name} fuses the 'mean' and 'sum' reductions only, got {reduction!r}")
+    return reduction == 'mean'
+
+
 def deterministic_default():
     """The Python host asks for the bit-reproducible gradient accumulation (include/ssg_hip.h, ssg_grad_fix_bytes)
     unless SSG_DETERMINISTIC=0 is set: measured +3 % on the benchmark step (1.64 vs 1.59 ms), for gradients that
@@ -104,17 +134,13 @@ def edge_list(mask=None, gt=None, mask_stride=0, lap_threshold=20.0, capacity=No
     L = _lib.lib()
     if mask is not None:
         _need_gpu(mask)
-        if mask.dtype == torch.uint8 or mask.dtype == torch.bool:   # edge pixel <=> value 1 (True), like `mask == 1`
-            src, kind = mask.contiguous().view(torch.uint8), 1
-        else:
-            src, kind = _f32c(mask), 0
+        src, kind = _mask_kind(mask, None)
         B, c1, H, W = src.shape
     else:
         _need_gpu(gt)
-        src, kind = _f32c(gt), 2
+        src = _f32c(gt)
         B, c1, H, W = src.shape
-        if c1 != 3:
-            raise ValueError("Laplacian edge mask needs a 3-channel image")
+        kind = _mask_kind(None, c1)[1]
     if capacity is None:
         capacity = B * H * W
     dev = src.device
@@ -124,10 +150,8 @@ def edge_list(mask=None, gt=None, mask_stride=0, lap_threshold=20.0, capacity=No
     order = torch.empty(max(capacity, 1), dtype=torch.int32, device=dev) if order else None
     plan = torch.empty(L.ssg_forward_plan_bytes(B, H, W, capacity) // 4, dtype=torch.int32, device=dev) if plan else None
     scratch = torch.empty(L.ssg_edge_scratch_bytes(B, H, W), dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):   # launches go to the tensors' GPU, whatever the current device is
-        _lib.check(L.ssg_edge_list(_ptr(src), kind, c1, B, H, W, int(mask_stride or 0), float(lap_threshold), int(ks),
-                                   _ptr(edges), capacity, _ptr(counts), _ptr(rank), _ptr(order), _ptr(plan),
-                                   _ptr(scratch), _stream()))
+    _launch(dev, L.ssg_edge_list, _ptr(src), kind, c1, B, H, W, int(mask_stride or 0), float(lap_threshold), int(ks),
+            _ptr(edges), capacity, _ptr(counts), _ptr(rank), _ptr(order), _ptr(plan), _ptr(scratch))
     return EdgeList(edges, counts, rank, order, plan, ks)
 
 
@@ -161,9 +185,8 @@ def edge_mask_laplacian(gt, lap_threshold=20.0, mask_stride=0):
     if C != 3:
         raise ValueError("Laplacian edge mask needs a 3-channel image")
     out = torch.empty((B, H, W), dtype=torch.uint8, device=g.device)
-    with torch.cuda.device(g.device):
-        _lib.check(_lib.lib().ssg_edge_mask_laplacian(_ptr(g), B, H, W, float(lap_threshold), int(mask_stride or 0),
-                                                      _ptr(out), _stream()))
+    _launch(g.device, _lib.lib().ssg_edge_mask_laplacian, _ptr(g), B, H, W, float(lap_threshold), int(mask_stride or 0),
+            _ptr(out))
     return out
 
 
@@ -177,10 +200,9 @@ class _SSGMapFn(torch.autograd.Function):
         f_order, f_rank, f_plan = fwd if fwd is not None else (order, None, None)
         B, C, H, W = x.shape
         ssg = torch.empty((n_rows, ks * ks), dtype=torch.float32, device=x.device)
-        with torch.cuda.device(x.device):
-            _lib.check(_lib.lib().ssg_map_forward(_ptr(x), None, B, C, H, W, _ptr(edges), _ptr(f_order), _ptr(f_rank),
-                                                  _ptr(f_plan), _ptr(counts), n_rows, ks, kw, float(sigma), float(eps),
-                                                  int(bool(generalization)), _ptr(ssg), None, None, _stream()))
+        _launch(x.device, _lib.lib().ssg_map_forward, _ptr(x), None, B, C, H, W, _ptr(edges), _ptr(f_order), _ptr(f_rank),
+                _ptr(f_plan), _ptr(counts), n_rows, ks, kw, float(sigma), float(eps), int(bool(generalization)),
+                _ptr(ssg), None, None)
         ctx.save_for_backward(x, edges, counts, ssg)
         ctx.in_dtype = img.dtype
         ctx.order = order
@@ -202,10 +224,8 @@ class _SSGMapFn(torch.autograd.Function):
         if rank is not None and plan is not None:
             scratch = torch.empty(L.ssg_backward_scratch_bytes(n_rows, ks), dtype=torch.uint8, device=x.device)
         fix = _grad_fix(ctx.det, x)
-        with torch.cuda.device(x.device):
-            _lib.check(L.ssg_map_backward(_ptr(x), B, C, H, W, _ptr(edges), _ptr(ctx.order), _ptr(rank), _ptr(plan),
-                                          _ptr(counts), n_rows, ks, kw, sigma, gen, _ptr(ssg), _ptr(g), _ptr(grad),
-                                          _ptr(scratch), _ptr(fix), _stream()))
+        _launch(x.device, L.ssg_map_backward, _ptr(x), B, C, H, W, _ptr(edges), _ptr(ctx.order), _ptr(rank), _ptr(plan),
+                _ptr(counts), n_rows, ks, kw, sigma, gen, _ptr(ssg), _ptr(g), _ptr(grad), _ptr(scratch), _ptr(fix))
         return grad.to(ctx.in_dtype), None, None, None, None, None, None, None, None, None, None, None
 
 
@@ -247,23 +267,28 @@ class _SSGLossFn(torch.autograd.Function):
         rsc = None
         if f_rank is not None and f_plan is not None and (ks, kw, C) in ((25, 9, 3), (49, 13, 3)):
             rsc = torch.empty(2 * max(n_rows, 1), dtype=torch.float64, device=dev)
-        _lib.check(L.ssg_map_forward(_ptr(x), _ptr(y), B, C, H, W, _ptr(edges), _ptr(f_order), _ptr(f_rank), _ptr(f_plan),
-                                     _ptr(counts), n_rows, ks, kw, sigma, eps, gen, _ptr(ssg_sr), _ptr(ssg_gt),
-                                     _ptr(rsc), _stream()))
+        _launch(dev, L.ssg_map_forward, _ptr(x), _ptr(y), B, C, H, W, _ptr(edges), _ptr(f_order), _ptr(f_rank),
+                _ptr(f_plan), _ptr(counts), n_rows, ks, kw, sigma, eps, gen, _ptr(ssg_sr), _ptr(ssg_gt), _ptr(rsc))
         fix = _grad_fix(det, x) if want_grad else None
-        _lib.check(L.ssg_loss_backward(_ptr(x), B, C, H, W, _ptr(edges), _ptr(order), _ptr(f_rank), _ptr(f_plan),
-                                       _ptr(counts), n_rows, ks, kw, sigma, gen, _ptr(ssg_sr), _ptr(ssg_gt), w_l1,
-                                       w_kl, _ptr(upstream), _ptr(loss), _ptr(grad), _ptr(scratch), _ptr(fix), _ptr(rsc),
-                                       1, _stream()))   # (the rows die with this call: no write-back)
+        _launch(dev, L.ssg_loss_backward, _ptr(x), B, C, H, W, _ptr(edges), _ptr(order), _ptr(f_rank), _ptr(f_plan),
+                _ptr(counts), n_rows, ks, kw, sigma, gen, _ptr(ssg_sr), _ptr(ssg_gt), w_l1, w_kl, _ptr(upstream),
+                _ptr(loss), _ptr(grad), _ptr(scratch), _ptr(fix), _ptr(rsc), 1)   # (the rows die with this call: no write-back)
         return loss, grad
+
+    @staticmethod
+    def scaled_or_redone(grad, g_l1, g_kl, redo):
+        """d(l1 + kl)/d sr for the upstream gradients of l1 and kl: the saved gradient scaled when both are one and the
+        same scalar, else redo(device pair of the two) -- the step again with them."""
+        if g_l1.data_ptr() == g_kl.data_ptr() and g_l1.numel() == 1 and g_kl.numel() == 1:
+            return grad * g_l1.to(torch.float32).reshape(())
+        return redo(torch.stack([g_l1.to(torch.float32).reshape(()), g_kl.to(torch.float32).reshape(())]).contiguous())
 
     @staticmethod
     def forward(ctx, sr, gt, edges, counts, n_rows, ks, kw, sigma, eps, generalization, w_l1, w_kl, order, fwd, det):
         x, y = _f32c(sr), _f32c(gt)
         cfg = (n_rows, ks, kw, float(sigma), float(eps), int(bool(generalization)), float(w_l1), float(w_kl))
         want_grad = bool(ctx.needs_input_grad[0])
-        with torch.cuda.device(x.device):
-            loss, grad = _SSGLossFn._run(x, y, edges, counts, *cfg, order, fwd, None, want_grad, det)
+        loss, grad = _SSGLossFn._run(x, y, edges, counts, *cfg, order, fwd, None, want_grad, det)
         ctx.cfg, ctx.order, ctx.fwd, ctx.det = cfg, order, fwd, det
         ctx.in_dtype = sr.dtype
         if want_grad:
@@ -274,13 +299,8 @@ class _SSGLossFn(torch.autograd.Function):
     @torch.autograd.function.once_differentiable
     def backward(ctx, g_l1, g_kl):
         x, y, edges, counts, grad = ctx.saved_tensors
-        same = (g_l1.data_ptr() == g_kl.data_ptr() and g_l1.numel() == 1 and g_kl.numel() == 1)
-        if same:
-            out = grad * g_l1.to(torch.float32).reshape(())
-        else:
-            up = torch.stack([g_l1.to(torch.float32).reshape(()), g_kl.to(torch.float32).reshape(())]).contiguous()
-            with torch.cuda.device(x.device):
-                _, out = _SSGLossFn._run(x, y, edges, counts, *ctx.cfg, ctx.order, ctx.fwd, up, True, ctx.det)
+        out = _SSGLossFn.scaled_or_redone(grad, g_l1, g_kl, lambda up: _SSGLossFn._run(
+            x, y, edges, counts, *ctx.cfg, ctx.order, ctx.fwd, up, True, ctx.det)[1])
         return (out.to(ctx.in_dtype),) + (None,) * 14
 
 
@@ -306,16 +326,8 @@ class _SSGFusedFn(torch.autograd.Function):
         L = _lib.lib()
         x, y = _f32c(sr), _f32c(gt)
         B, C, H, W = x.shape
-        if mask is None:
-            kind, mc, mp = 2, 3, None
-            if C != 3:
-                raise ValueError("Laplacian edge mask needs a 3-channel image")
-        elif mask.dtype == torch.uint8 or mask.dtype == torch.bool:
-            mp = mask.contiguous().view(torch.uint8)
-            kind, mc = 1, mp.shape[1]
-        else:
-            mp = _f32c(mask)
-            kind, mc = 0, mp.shape[1]
+        mp, kind = _mask_kind(mask, C)
+        mc = 3 if mp is None else mp.shape[1]
         want_grad = bool(ctx.needs_input_grad[0])
         dev = x.device
         loss = torch.empty(2, dtype=torch.float32, device=dev)
@@ -323,11 +335,9 @@ class _SSGFusedFn(torch.autograd.Function):
         nb = L.ssg_loss_workspace_bytes(B, H, W, cap, ks) + L.ssg_loss_rows_bytes(cap, ks)
         ws = torch.empty(nb, dtype=torch.uint8, device=dev)
         fix = _grad_fix(det, x) if want_grad else None
-        with torch.cuda.device(dev):
-            _lib.check(L.ssg_loss_step(_ptr(x), _ptr(y), _ptr(mp), kind, mc, B, C, H, W, ks, kw, float(sigma),
-                                       float(eps), int(bool(generalization)), float(w_l1), float(w_kl),
-                                       int(mask_stride or 0), float(lap_threshold), cap, None, None, _ptr(counts),
-                                       _ptr(loss), _ptr(grad), _ptr(ws), nb, _ptr(fix), _stream()))
+        _launch(dev, L.ssg_loss_step, _ptr(x), _ptr(y), _ptr(mp), kind, mc, B, C, H, W, ks, kw, float(sigma), float(eps),
+                int(bool(generalization)), float(w_l1), float(w_kl), int(mask_stride or 0), float(lap_threshold), cap,
+                None, None, _ptr(counts), _ptr(loss), _ptr(grad), _ptr(ws), nb, _ptr(fix))
         ctx.cfg = (cap, ks, kw, sigma, eps, generalization, w_l1, w_kl, mask_stride, lap_threshold, det)
         ctx.in_dtype = sr.dtype
         ctx.has_mask = mask is not None
@@ -340,17 +350,15 @@ class _SSGFusedFn(torch.autograd.Function):
     def backward(ctx, g_l1, g_kl):
         x, y, grad = ctx.saved_tensors[:3]
         mask = ctx.saved_tensors[3] if ctx.has_mask else None
-        same = (g_l1.data_ptr() == g_kl.data_ptr() and g_l1.numel() == 1 and g_kl.numel() == 1)
-        if same:
-            out = grad * g_l1.to(torch.float32).reshape(())
-        else:
+
+        def redo(up):
             cap, ks, kw, sigma, eps, gen, w_l1, w_kl, stride, thr, det = ctx.cfg
-            up = torch.stack([g_l1.to(torch.float32).reshape(()), g_kl.to(torch.float32).reshape(())]).contiguous()
             el = edge_list(mask=mask, gt=y if mask is None else None, mask_stride=stride, lap_threshold=thr,
                            capacity=cap, ks=ks)
-            with torch.cuda.device(x.device):
-                _, out = _SSGLossFn._run(x, y, el.edges, el.counts, cap, ks, kw, float(sigma), float(eps),
-                                         int(bool(gen)), float(w_l1), float(w_kl), el.order, el.fwd, up, True, det)
+            return _SSGLossFn._run(x, y, el.edges, el.counts, cap, ks, kw, float(sigma), float(eps), int(bool(gen)),
+                                   float(w_l1), float(w_kl), el.order, el.fwd, up, True, det)[1]
+
+        out = _SSGLossFn.scaled_or_redone(grad, g_l1, g_kl, redo)
         return (out.to(ctx.in_dtype),) + (None,) * 14
 
 
@@ -454,6 +462,32 @@ class LossStep:
         return self.loss, self.grad
 
 
+# ------------------------------------- the fused pixel losses: LDL, best-buddy, back-projection (ssg_pixel.hpp) ----
+class _FusedLossFn(torch.autograd.Function):
+    """A scalar loss whose ONE C call produces the loss and d loss / d x together: ldl_loss, bbl_loss and bp_loss.
+    `call(want_grad)` runs the family's checks and its C call and returns (loss (1,) fp32, gradient or None); only the
+    gradient is kept, and backward() scales it by the incoming one (the pattern of _SSGLossFn)."""
+
+    @staticmethod
+    def forward(ctx, x, call):
+        loss, grad = call(bool(ctx.needs_input_grad[0]))
+        if grad is not None:
+            ctx.save_for_backward(grad)
+        ctx.in_dtype = x.dtype
+        return loss[0]
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        grad, = ctx.saved_tensors
+        return (grad * g.to(torch.float32).reshape(())).to(ctx.in_dtype), None
+
+
+def _loss_and_grad(x, want_grad):
+    """The two outputs of a fused loss call on the fp32 input x: (loss (1,), gradient like x or None)."""
+    return torch.empty(1, dtype=torch.float32, device=x.device), torch.empty_like(x) if want_grad else None
+
+
 # ------------------------------------------------------------------------- LDL's artifact map (ssg_ldl.hip) ----
 def _ldl_prepare(output, gt, ema, ksize):
     """fp32 contiguous copies of (output, gt, ema) after the checks every LDL entry point makes."""
@@ -468,11 +502,6 @@ def _ldl_prepare(output, gt, ema, ksize):
     return _f32c(output), _f32c(gt), None if ema is None else _f32c(ema), int(ksize)
 
 
-def _ldl_workspace(B, H, W, dev):
-    n = _lib.lib().ssg_ldl_workspace_bytes(B, H, W)
-    return torch.empty(max(n, 1), dtype=torch.uint8, device=dev), n
-
-
 class _ArtifactMapFn(torch.autograd.Function):
     """w = get_(refined_)artifact_map(gt, output, ema, k) (loss_util.py:129-161), (B,1,H,W); backward: one
     ssg_artifact_map_backward call for any upstream dL/dw."""
@@ -482,10 +511,8 @@ class _ArtifactMapFn(torch.autograd.Function):
         x, y, z, k = _ldl_prepare(output, gt, ema, k)
         B, C, H, W = x.shape
         w = torch.empty((B, 1, H, W), dtype=torch.float32, device=x.device)
-        ws, nb = _ldl_workspace(B, H, W, x.device)
-        with torch.cuda.device(x.device):
-            _lib.check(_lib.lib().ssg_artifact_map(_ptr(x), _ptr(y), _ptr(z), B, C, H, W, k, _ptr(w), _ptr(ws), nb,
-                                                   _stream()))
+        ws, nb = _workspace(_lib.lib().ssg_ldl_workspace_bytes(B, H, W), x.device)
+        _launch(x.device, _lib.lib().ssg_artifact_map, _ptr(x), _ptr(y), _ptr(z), B, C, H, W, k, _ptr(w), _ptr(ws), nb)
         if ctx.needs_input_grad[0]:
             ctx.save_for_backward(x, y, z)
         ctx.k, ctx.in_dtype = k, output.dtype
@@ -498,10 +525,9 @@ class _ArtifactMapFn(torch.autograd.Function):
         B, C, H, W = x.shape
         gw = _f32c(grad_w)
         grad = torch.empty_like(x)
-        ws, nb = _ldl_workspace(B, H, W, x.device)
-        with torch.cuda.device(x.device):
-            _lib.check(_lib.lib().ssg_artifact_map_backward(_ptr(x), _ptr(y), _ptr(z), _ptr(gw), B, C, H, W, ctx.k,
-                                                            _ptr(grad), _ptr(ws), nb, _stream()))
+        ws, nb = _workspace(_lib.lib().ssg_ldl_workspace_bytes(B, H, W), x.device)
+        _launch(x.device, _lib.lib().ssg_artifact_map_backward, _ptr(x), _ptr(y), _ptr(z), _ptr(gw), B, C, H, W, ctx.k,
+                _ptr(grad), _ptr(ws), nb)
         return grad.to(ctx.in_dtype), None, None, None
 
 
@@ -512,39 +538,21 @@ def artifact_map(output, gt, ema=None, ksize=7):
     return _ArtifactMapFn.apply(output, gt, ema, ksize)
 
 
-class _LdlLossFn(torch.autograd.Function):
-    """loss_weight * mean (or sum) |w*output - w*gt| with w = artifact_map(output, gt, ema): ONE ssg_ldl_loss call
-    produces the loss and d loss / d output together (the gradient through the map included); backward() only scales
-    that gradient by the incoming one (the pattern of _SSGLossFn)."""
-
-    @staticmethod
-    def forward(ctx, output, gt, ema, k, loss_weight, mean):
-        x, y, z, k = _ldl_prepare(output, gt, ema, k)
-        B, C, H, W = x.shape
-        loss = torch.empty(1, dtype=torch.float32, device=x.device)
-        grad = torch.empty_like(x) if ctx.needs_input_grad[0] else None
-        ws, nb = _ldl_workspace(B, H, W, x.device)
-        with torch.cuda.device(x.device):
-            _lib.check(_lib.lib().ssg_ldl_loss(_ptr(x), _ptr(y), _ptr(z), B, C, H, W, k, float(loss_weight),
-                                               int(bool(mean)), _ptr(loss), _ptr(grad), _ptr(ws), nb, _stream()))
-        if grad is not None:
-            ctx.save_for_backward(grad)
-        ctx.in_dtype = output.dtype
-        return loss[0]
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, g):
-        grad, = ctx.saved_tensors
-        return (grad * g.to(torch.float32).reshape(())).to(ctx.in_dtype), None, None, None, None, None
-
-
 def ldl_loss(output, gt, ema=None, ksize=7, loss_weight=1.0, reduction='mean'):
     """L1Loss(w * output, w * gt) with w = artifact_map(output, gt, ema, ksize), fused: the callers'
     ldlssl_model.py:220-224 / realesrgan_model.py:222-226 in one call.  reduction 'mean' or 'sum'."""
-    if reduction not in ('mean', 'sum'):
-        raise ValueError(f"ssl_amd: ldl_loss fuses the 'mean' and 'sum' reductions only, got {reduction!r}")
-    return _LdlLossFn.apply(output, gt, ema, ksize, loss_weight, reduction == 'mean')
+    mean = _reduction_is_mean("ldl_loss", reduction)
+
+    def call(want_grad):
+        x, y, z, k = _ldl_prepare(output, gt, ema, ksize)
+        B, C, H, W = x.shape
+        loss, grad = _loss_and_grad(x, want_grad)
+        ws, nb = _workspace(_lib.lib().ssg_ldl_workspace_bytes(B, H, W), x.device)
+        _launch(x.device, _lib.lib().ssg_ldl_loss, _ptr(x), _ptr(y), _ptr(z), B, C, H, W, k, float(loss_weight),
+                int(mean), _ptr(loss), _ptr(grad), _ptr(ws), nb)
+        return loss, grad
+
+    return _FusedLossFn.apply(output, call)
 
 
 class _LocalVarFn(torch.autograd.Function):
@@ -558,10 +566,8 @@ class _LocalVarFn(torch.autograd.Function):
         r = _f32c(residual)
         B, C, H, W = r.shape
         v = torch.empty_like(r)
-        ws, nb = _ldl_workspace(B * C, H, W, r.device)
-        with torch.cuda.device(r.device):
-            _lib.check(_lib.lib().ssg_local_variance(_ptr(r), B * C, H, W, int(k), _ptr(v), None, None, _ptr(ws), nb,
-                                                     _stream()))
+        ws, nb = _workspace(_lib.lib().ssg_ldl_workspace_bytes(B * C, H, W), r.device)
+        _launch(r.device, _lib.lib().ssg_local_variance, _ptr(r), B * C, H, W, int(k), _ptr(v), None, None, _ptr(ws), nb)
         if ctx.needs_input_grad[0]:
             ctx.save_for_backward(r)
         ctx.k, ctx.in_dtype = int(k), residual.dtype
@@ -574,10 +580,9 @@ class _LocalVarFn(torch.autograd.Function):
         B, C, H, W = r.shape
         gv = _f32c(grad_v)
         grad = torch.empty_like(r)
-        ws, nb = _ldl_workspace(B * C, H, W, r.device)
-        with torch.cuda.device(r.device):
-            _lib.check(_lib.lib().ssg_local_variance(_ptr(r), B * C, H, W, ctx.k, None, _ptr(gv), _ptr(grad), _ptr(ws),
-                                                     nb, _stream()))
+        ws, nb = _workspace(_lib.lib().ssg_ldl_workspace_bytes(B * C, H, W), r.device)
+        _launch(r.device, _lib.lib().ssg_local_variance, _ptr(r), B * C, H, W, ctx.k, None, _ptr(gv), _ptr(grad), _ptr(ws),
+                nb)
         return grad.to(ctx.in_dtype), None
 
 
@@ -608,11 +613,6 @@ def _bbl_prepare(x, gt, alpha, beta, ksize, stride):
     return _f32c(x), _f32c(gt), ksize, stride
 
 
-def _bbl_workspace(B, C, H, W, k, s, dev):
-    n = _lib.lib().ssg_bbl_workspace_bytes(B, C, H, W, k, s)
-    return torch.empty(max(n, 1), dtype=torch.uint8, device=dev), n
-
-
 def _bbl_patches(H, W, k, s):
     return ((H - k) // s + 1) * ((W - k) // s + 1)
 
@@ -622,14 +622,13 @@ def bbl_search(x, gt, alpha=1.0, beta=1.0, ksize=3, stride=3, want_p1=True, want
     ind indexes cat[p2, unfold(gt_2), unfold(gt_4)], the lowest index among equal fp32 scores."""
     xs, gs, k, s = _bbl_prepare(x, gt, alpha, beta, ksize, stride)
     B, C, H, W = xs.shape
-    ws, nb = _bbl_workspace(B, C, H, W, k, s, xs.device)
+    ws, nb = _workspace(_lib.lib().ssg_bbl_workspace_bytes(B, C, H, W, k, s), xs.device)
     N, d = max(_bbl_patches(H, W, k, s), 0), C * k * k
     ind = torch.empty((B, N), dtype=torch.int32, device=xs.device)
     p1 = torch.empty((B, N, d), dtype=torch.float32, device=xs.device) if want_p1 else None
     sel = torch.empty((B, N, d), dtype=torch.float32, device=xs.device) if want_sel else None
-    with torch.cuda.device(xs.device):
-        _lib.check(_lib.lib().ssg_bbl_search(_ptr(xs), _ptr(gs), B, C, H, W, k, s, float(alpha), float(beta),
-                                             _ptr(ind), _ptr(p1), _ptr(sel), _ptr(ws), nb, _stream()))
+    _launch(xs.device, _lib.lib().ssg_bbl_search, _ptr(xs), _ptr(gs), B, C, H, W, k, s, float(alpha), float(beta),
+            _ptr(ind), _ptr(p1), _ptr(sel), _ptr(ws), nb)
     return ind, p1, sel
 
 
@@ -659,39 +658,21 @@ def bbl_patches(x, gt, alpha=1.0, beta=1.0, ksize=3, stride=3):
     return _BBLPatchesFn.apply(x, gt, alpha, beta, ksize, stride)
 
 
-class _BBLLossFn(torch.autograd.Function):
-    """loss_weight * mean (or sum) |p1 - sel_p2|: ONE ssg_bbl_loss call produces the loss and d loss / d x together;
-    backward() only scales that gradient by the incoming one (the pattern of _LdlLossFn)."""
-
-    @staticmethod
-    def forward(ctx, x, gt, alpha, beta, k, s, loss_weight, mean):
-        xs, gs, k, s = _bbl_prepare(x, gt, alpha, beta, k, s)
-        B, C, H, W = xs.shape
-        loss = torch.empty(1, dtype=torch.float32, device=xs.device)
-        grad = torch.empty_like(xs) if ctx.needs_input_grad[0] else None
-        ws, nb = _bbl_workspace(B, C, H, W, k, s, xs.device)
-        with torch.cuda.device(xs.device):
-            _lib.check(_lib.lib().ssg_bbl_loss(_ptr(xs), _ptr(gs), B, C, H, W, k, s, float(alpha), float(beta),
-                                               float(loss_weight), int(bool(mean)), _ptr(loss), _ptr(grad), None,
-                                               _ptr(ws), nb, _stream()))
-        if grad is not None:
-            ctx.save_for_backward(grad)
-        ctx.in_dtype = x.dtype
-        return loss[0]
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, g):
-        grad, = ctx.saved_tensors
-        return (grad * g.to(torch.float32).reshape(())).to(ctx.in_dtype), None, None, None, None, None, None, None
-
-
 def bbl_loss(x, gt, alpha=1.0, beta=1.0, ksize=3, stride=3, loss_weight=1.0, reduction='mean'):
     """L1Loss(*BBL(alpha, beta, ksize, 0, stride).forward(x, gt)), fused: the caller's bebyganssl_model.py:723-724 in
     one call.  reduction 'mean' or 'sum'."""
-    if reduction not in ('mean', 'sum'):
-        raise ValueError(f"ssl_amd: bbl_loss fuses the 'mean' and 'sum' reductions only, got {reduction!r}")
-    return _BBLLossFn.apply(x, gt, alpha, beta, ksize, stride, loss_weight, reduction == 'mean')
+    mean = _reduction_is_mean("bbl_loss", reduction)
+
+    def call(want_grad):
+        xs, gs, k, s = _bbl_prepare(x, gt, alpha, beta, ksize, stride)
+        B, C, H, W = xs.shape
+        loss, grad = _loss_and_grad(xs, want_grad)
+        ws, nb = _workspace(_lib.lib().ssg_bbl_workspace_bytes(B, C, H, W, k, s), xs.device)
+        _launch(xs.device, _lib.lib().ssg_bbl_loss, _ptr(xs), _ptr(gs), B, C, H, W, k, s, float(alpha), float(beta),
+                float(loss_weight), int(mean), _ptr(loss), _ptr(grad), None, _ptr(ws), nb)
+        return loss, grad
+
+    return _FusedLossFn.apply(x, call)
 
 
 def flat_mask(img, kernel_size=11, std_thresh=0.025):
@@ -703,9 +684,7 @@ def flat_mask(img, kernel_size=11, std_thresh=0.025):
     x = _f32c(img)
     B, _, H, W = x.shape
     mask = torch.empty((B, 1, H, W), dtype=torch.float32, device=x.device)
-    with torch.cuda.device(x.device):
-        _lib.check(_lib.lib().ssg_flat_mask(_ptr(x), B, H, W, int(kernel_size), float(std_thresh), _ptr(mask),
-                                            _stream()))
+    _launch(x.device, _lib.lib().ssg_flat_mask, _ptr(x), B, H, W, int(kernel_size), float(std_thresh), _ptr(mask))
     return mask.to(img.dtype)
 
 
@@ -753,8 +732,7 @@ class _BPDownsampleFn(torch.autograd.Function):
         H, W = xs.shape[-2:]
         P = xs.numel() // (H * W)
         y = torch.empty(tuple(xs.shape[:-2]) + (H // s, W // s), dtype=torch.float32, device=xs.device)
-        with torch.cuda.device(xs.device):
-            _lib.check(_lib.lib().ssg_bp_downsample(_ptr(xs), P, H, W, s, _ptr(y), _stream()))
+        _launch(xs.device, _lib.lib().ssg_bp_downsample, _ptr(xs), P, H, W, s, _ptr(y))
         ctx.geom, ctx.in_dtype = (tuple(xs.shape), P, s), x.dtype
         return y.to(x.dtype)
 
@@ -764,9 +742,7 @@ class _BPDownsampleFn(torch.autograd.Function):
         shape, P, s = ctx.geom
         gy = _f32c(grad_y)
         grad = torch.empty(shape, dtype=torch.float32, device=gy.device)
-        with torch.cuda.device(gy.device):
-            _lib.check(_lib.lib().ssg_bp_downsample_backward(_ptr(gy), P, shape[-2], shape[-1], s, _ptr(grad),
-                                                             _stream()))
+        _launch(gy.device, _lib.lib().ssg_bp_downsample_backward, _ptr(gy), P, shape[-2], shape[-1], s, _ptr(grad))
         return grad.to(ctx.in_dtype), None
 
 
@@ -777,37 +753,19 @@ def bp_downsample(x, s):
     return _BPDownsampleFn.apply(x, s)
 
 
-class _BPLossFn(torch.autograd.Function):
-    """loss_weight * mean (or sum) |imresize(x, 1 / s) - lq|: ONE ssg_bp_loss call produces the loss and d loss / d x
-    together; backward() only scales that gradient by the incoming one (the pattern of _BBLLossFn)."""
-
-    @staticmethod
-    def forward(ctx, x, lq, s, loss_weight, mean):
-        xs, ls, s = _bp_prepare(x, lq, s)
-        H, W = xs.shape[-2:]
-        P = xs.numel() // (H * W)
-        loss = torch.empty(1, dtype=torch.float32, device=xs.device)
-        grad = torch.empty_like(xs) if ctx.needs_input_grad[0] else None
-        nb = _lib.lib().ssg_bp_workspace_bytes(P, H, W, s)
-        ws = torch.empty(max(nb, 1), dtype=torch.uint8, device=xs.device)
-        with torch.cuda.device(xs.device):
-            _lib.check(_lib.lib().ssg_bp_loss(_ptr(xs), _ptr(ls), P, H, W, s, float(loss_weight), int(bool(mean)),
-                                              _ptr(loss), _ptr(grad), None, _ptr(ws), nb, _stream()))
-        if grad is not None:
-            ctx.save_for_backward(grad)
-        ctx.in_dtype = x.dtype
-        return loss[0]
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, g):
-        grad, = ctx.saved_tensors
-        return (grad * g.to(torch.float32).reshape(())).to(ctx.in_dtype), None, None, None, None
-
-
 def bp_loss(x, lq, s=4, loss_weight=1.0, reduction='mean'):
     """L1Loss(imresize(x, scale=1 / s), lq), fused: the caller's bebyganssl_model.py:727-731 in one call.  reduction
     'mean' or 'sum'."""
-    if reduction not in ('mean', 'sum'):
-        raise ValueError(f"ssl_amd: bp_loss fuses the 'mean' and 'sum' reductions only, got {reduction!r}")
-    return _BPLossFn.apply(x, lq, s, loss_weight, reduction == 'mean')
+    mean = _reduction_is_mean("bp_loss", reduction)
+
+    def call(want_grad):
+        xs, ls, f = _bp_prepare(x, lq, s)
+        H, W = xs.shape[-2:]
+        P = xs.numel() // (H * W)
+        loss, grad = _loss_and_grad(xs, want_grad)
+        ws, nb = _workspace(_lib.lib().ssg_bp_workspace_bytes(P, H, W, f), xs.device)
+        _launch(xs.device, _lib.lib().ssg_bp_loss, _ptr(xs), _ptr(ls), P, H, W, f, float(loss_weight), int(mean),
+                _ptr(loss), _ptr(grad), None, _ptr(ws), nb)
+        return loss, grad
+
+    return _FusedLossFn.apply(x, call)

@@ -332,17 +332,43 @@ def test_host_sizes_match_the_recorded_fixture():
         assert gen.measure(L, *row[:5]) == row[5:], row[:5]
 
 
-def test_host_header_stands_alone(tmp_path):
-    """ssg_host.hpp -- the one declaration of every host function that crosses a file boundary -- compiles on its own
-    with -Wall -Werror, in the product and the profiling configuration (no kernel, a second or two)."""
+def test_loss_workspace_sizes_match_the_recorded_fixture():
+    """Fixture F22 (tests/golden/make_golden_loss_sizes.py): ssg_ldl_workspace_bytes, ssg_bbl_workspace_bytes and
+    ssg_bp_workspace_bytes over batch sizes, image sizes on and off the tile and block edges, the best-buddy window
+    geometries, the three downsampling factors and the shapes refused with 0 -- EXACTLY as recorded before the three
+    workspaces were laid out by the library's one carver."""
+    import importlib.util
+    import json
     from ssl_amd import _lib
-    tu = tmp_path / "host_header_only.hip"
-    tu.write_text('#include "ssg_host.hpp"\n')
-    for define in ([], ["-DSSG_PROFILE"]):
-        cmd = [os.environ.get("HIPCC", "/opt/rocm/bin/hipcc"), "-std=c++17", "--offload-arch=gfx950", "-Wall", "-Werror", "-I", _lib.CSRC] + define + \
-              ["-c", str(tu), "-o", str(tmp_path / "host_header_only.o")]
-        out = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
-        assert out.returncode == 0, out.stdout
+    spec = importlib.util.spec_from_file_location("make_golden_loss_sizes",
+                                                  os.path.join(ROOT, "tests", "golden", "make_golden_loss_sizes.py"))
+    gen = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(gen)
+    fix = json.load(open(os.path.join(ROOT, "tests", "golden", "f22_loss_sizes.json")))
+    L = _lib.lib()
+    assert fix["abi_version"] == L.ssg_abi_version()
+    for name, fn, cases in gen.FAMILIES:
+        rows = fix[name]
+        assert [tuple(r[:-1]) for r in rows] == list(cases()), name
+        assert sum(r[-1] == 0 for r in rows) >= 4 and sum(r[-1] > 0 for r in rows) >= 40, name   # refused and served shapes
+        for row in rows:
+            assert getattr(L, fn)(*row[:-1]) == row[-1], (name, row)
+    assert max(r[0] * -(-(r[1] // r[3]) // 8) * -(-(r[2] // r[3]) // 16) for r in fix["bp"] if r[-1]) > 4096
+
+
+def test_host_header_stands_alone(tmp_path):
+    """ssg_host.hpp -- the one declaration of every host function that crosses a file boundary -- and ssg_pixel.hpp --
+    what the three pixel-loss files share -- each compile on their own with -Wall -Werror, in the product and the
+    profiling configuration (no kernel, a second or two)."""
+    from ssl_amd import _lib
+    for header in ("ssg_host.hpp", "ssg_pixel.hpp"):
+        tu = tmp_path / "host_header_only.hip"
+        tu.write_text(f'#include "{header}"\n')
+        for define in ([], ["-DSSG_PROFILE"]):
+            cmd = [os.environ.get("HIPCC", "/opt/rocm/bin/hipcc"), "-std=c++17", "--offload-arch=gfx950", "-Wall", "-Werror", "-I", _lib.CSRC] + define + \
+                  ["-c", str(tu), "-o", str(tmp_path / "host_header_only.o")]
+            out = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
+            assert out.returncode == 0, out.stdout
 
 
 def test_plan_built_for_another_tile_height_is_refused():

@@ -16,14 +16,13 @@ the fp64 contract evaluated at the GPU's validated indices; against the pure fp6
 |dloss| <= share of rows picked differently * max|p1 - sel| holds.
 
 Every comparison prints one `BBL64` line (pytest -s); profiles/bbl_parity.txt holds the table."""
-import ctypes
-
 import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
 
 import bbl_reference as R
+from raw_loss import RawLoss, replays_as_hip_graph, side_stream_equals_default_stream
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -306,28 +305,15 @@ def test_two_runs_are_bit_identical():
 
 
 # ----------------------------------------------------------------------------------- streams and graphs (C ABI) ----
-class _RawLoss:
-    """ssg_bbl_loss through the C ABI with preallocated loss / grad / ind / workspace, on torch's current stream."""
-
-    def __init__(self, shape):
-        from ssl_amd import _lib
-        self.L, self.shape = _lib.lib(), shape
-        B, C, H, W = shape
-        self.nb = self.L.ssg_bbl_workspace_bytes(B, C, H, W, 3, 3)
-        self.ws = torch.empty(self.nb, dtype=torch.uint8, device=DEV)
-        self.loss = torch.zeros(1, device=DEV)
-        self.grad = torch.zeros(shape, device=DEV)
-        self.ind = torch.zeros((B, (H // 3) * (W // 3)), dtype=torch.int32, device=DEV)
-
-    def __call__(self, x, g):
-        B, C, H, W = self.shape
-        rc = self.L.ssg_bbl_loss(x.data_ptr(), g.data_ptr(), B, C, H, W, 3, 3, 1.0, 1.0, 1.0, 1, self.loss.data_ptr(),
-                                 self.grad.data_ptr(), self.ind.data_ptr(), self.ws.data_ptr(), self.nb,
-                                 ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
-        assert rc == 0, rc
-
-    def outputs(self):
-        return self.loss.clone(), self.grad.clone(), self.ind.clone()
+def _raw_loss(shape):
+    """ssg_bbl_loss through the C ABI (raw_loss.RawLoss): loss, grad and ind."""
+    from ssl_amd import _lib
+    B, C, H, W = shape
+    L = _lib.lib()
+    return RawLoss(L.ssg_bbl_loss, L.ssg_bbl_workspace_bytes(B, C, H, W, 3, 3),
+                   lambda x, g: (x.data_ptr(), g.data_ptr(), B, C, H, W, 3, 3, 1.0, 1.0, 1.0, 1),
+                   (torch.zeros(1, device=DEV), torch.zeros(shape, device=DEV),
+                    torch.zeros((B, (H // 3) * (W // 3)), dtype=torch.int32, device=DEV)))
 
 
 def _dev_inputs(shape, seed):
@@ -337,44 +323,17 @@ def _dev_inputs(shape, seed):
 def test_side_stream_equals_default_stream():
     shape = (2, 3, 96, 81)
     x, g = _dev_inputs(shape, 41)
-    a, b = _RawLoss(shape), _RawLoss(shape)
-    a(x, g)
-    torch.cuda.synchronize()
-    side = torch.cuda.Stream()
-    side.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(side):
-        b(x, g)
-    side.synchronize()
-    for u, w in zip(a.outputs(), b.outputs()):
-        assert torch.equal(u, w)
+    a = side_stream_equals_default_stream(lambda: _raw_loss(shape), (x, g))
     loss, grad = hip_loss(x.cpu(), g.cpu(), 1.0, 1.0)
     assert torch.equal(a.loss[0].cpu(), loss) and torch.equal(a.grad.cpu(), grad)
 
 
 def test_loss_replays_as_hip_graph():
-    """One eager call, then the same call captured once (a single chain of four launches) and replayed after the
-    inputs were overwritten in place: the replay equals the eager result for the batch then in the buffers."""
+    """The captured call is a single chain of four launches."""
     shape = (2, 3, 96, 81)
     first, second = _dev_inputs(shape, 51), _dev_inputs(shape, 52)
-    x, g = (t.clone() for t in first)
-    eager, rec = _RawLoss(shape), _RawLoss(shape)
-    eager(x, g)
-    torch.cuda.synchronize()
-    graph = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(graph):
-        rec(x, g)
-    for batch in (first, second):
-        for dst, src in zip((x, g), batch):
-            dst.copy_(src)
-        eager(x, g)
-        torch.cuda.synchronize()
-        want = eager.outputs()
-        rec.loss.zero_(), rec.grad.zero_(), rec.ind.zero_()
-        graph.replay()
-        torch.cuda.synchronize()
-        for u, w in zip(rec.outputs(), want):
-            assert torch.equal(u, w)
-    first_run = _RawLoss(shape)
+    want = replays_as_hip_graph(lambda: _raw_loss(shape), (first, second))
+    first_run = _raw_loss(shape)
     first_run(*first)
     assert not torch.equal(first_run.outputs()[1], want[1])      # the second batch really differs
 

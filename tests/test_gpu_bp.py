@@ -13,7 +13,6 @@ pixels under its window are left out of the gradient comparison; every input mus
 ambiguous (asserted on the reference alone).
 
 Every comparison prints one `BP64` line (pytest -s) with the worst error over its bound."""
-import ctypes
 import functools
 
 import numpy as np
@@ -21,6 +20,7 @@ import pytest
 import torch
 
 import bp_reference as R
+from raw_loss import RawLoss, replays_as_hip_graph, side_stream_equals_default_stream
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -270,29 +270,16 @@ def test_best_buddy_and_back_projection_terms_together():
 
 
 # ----------------------------------------------------------------------------------- streams and graphs (C ABI) ----
-class _RawLoss:
-    """ssg_bp_loss through the C ABI with preallocated loss / grad / y / workspace, on torch's current stream."""
-
-    def __init__(self, shape, s=4):
-        from ssl_amd import _lib
-        self.L, self.shape, self.s = _lib.lib(), shape, s
-        B, C, H, W = shape
-        self.nb = self.L.ssg_bp_workspace_bytes(B * C, H, W, s)
-        assert 0 < self.nb <= 2 * B * C * (H // s) * (W // s) * 4 + 65536
-        self.ws = torch.empty(self.nb, dtype=torch.uint8, device=DEV)
-        self.loss = torch.zeros(1, device=DEV)
-        self.grad = torch.full(shape, float('nan'), device=DEV)
-        self.y = torch.full((B, C, H // s, W // s), float('nan'), device=DEV)
-
-    def __call__(self, x, lq):
-        B, C, H, W = self.shape
-        rc = self.L.ssg_bp_loss(x.data_ptr(), lq.data_ptr(), B * C, H, W, self.s, 1.0, 1, self.loss.data_ptr(),
-                                self.grad.data_ptr(), self.y.data_ptr(), self.ws.data_ptr(), self.nb,
-                                ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
-        assert rc == 0, rc
-
-    def outputs(self):
-        return self.loss.clone(), self.grad.clone(), self.y.clone()
+def _raw_loss(shape, s=4):
+    """ssg_bp_loss through the C ABI (raw_loss.RawLoss): loss, grad and y, the last two pre-filled with NaN."""
+    from ssl_amd import _lib
+    B, C, H, W = shape
+    L = _lib.lib()
+    nb = L.ssg_bp_workspace_bytes(B * C, H, W, s)
+    assert 0 < nb <= 2 * B * C * (H // s) * (W // s) * 4 + 65536
+    return RawLoss(L.ssg_bp_loss, nb, lambda x, lq: (x.data_ptr(), lq.data_ptr(), B * C, H, W, s, 1.0, 1),
+                   (torch.zeros(1, device=DEV), torch.full(shape, float('nan'), device=DEV),
+                    torch.full((B, C, H // s, W // s), float('nan'), device=DEV)))
 
 
 def _dev_inputs(shape, s=4):
@@ -304,7 +291,7 @@ def _dev_inputs(shape, s=4):
 def test_every_gradient_element_is_written(s, shape):
     """grad_x and y_out pre-filled with NaN: the call leaves none, and equals the Python layer bit for bit."""
     x, lq = _dev_inputs(shape, s)
-    raw = _RawLoss(shape, s)
+    raw = _raw_loss(shape, s)
     raw(x, lq)
     torch.cuda.synchronize()
     loss, grad, y = raw.outputs()
@@ -317,45 +304,16 @@ def test_every_gradient_element_is_written(s, shape):
 
 def test_side_stream_equals_default_stream():
     shape = (2, 3, 48, 40)
-    x, lq = _dev_inputs(shape)
-    a, b = _RawLoss(shape), _RawLoss(shape)
-    a(x, lq)
-    torch.cuda.synchronize()
-    side = torch.cuda.Stream()
-    side.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(side):
-        b(x, lq)
-    side.synchronize()
-    for u, w in zip(a.outputs(), b.outputs()):
-        assert torch.equal(u, w)
+    side_stream_equals_default_stream(lambda: _raw_loss(shape), _dev_inputs(shape))
 
 
 def test_loss_replays_as_hip_graph():
-    """One eager call, then the same call captured once (a single chain of two launches on one stream) and replayed
-    after the inputs were overwritten in place: the replay equals the eager result for the batch then in the
-    buffers."""
+    """The captured call is a single chain of two launches on one stream."""
     shape = (2, 3, 48, 40)
     first = _dev_inputs(shape)
     second = tuple(t.flip(0).contiguous() * 0.9 for t in first)
-    x, lq = (t.clone() for t in first)
-    eager, rec = _RawLoss(shape), _RawLoss(shape)
-    eager(x, lq)
-    torch.cuda.synchronize()
-    graph = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(graph):
-        rec(x, lq)
-    for batch in (first, second):
-        for dst, src in zip((x, lq), batch):
-            dst.copy_(src)
-        eager(x, lq)
-        torch.cuda.synchronize()
-        want = eager.outputs()
-        rec.loss.zero_(), rec.grad.zero_(), rec.y.zero_()
-        graph.replay()
-        torch.cuda.synchronize()
-        for u, w in zip(rec.outputs(), want):
-            assert torch.equal(u, w)
-    first_run = _RawLoss(shape)
+    want = replays_as_hip_graph(lambda: _raw_loss(shape), (first, second))
+    first_run = _raw_loss(shape)
     first_run(*first)
     torch.cuda.synchronize()
     assert not torch.equal(first_run.outputs()[1], want[1])      # the second batch really differs

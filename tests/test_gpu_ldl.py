@@ -8,14 +8,13 @@ through the C ABI, reproducibility and the API.
 Bounds: 1e-5 of max|reference| for w, the loss (relative) and the gradient: the project's bar of every parity test,
 here against fp64.  Every fp64 comparison prints one `LDL64` line (pytest -s) with the measured ratios;
 profiles/ldl_fp64_parity.txt holds the table."""
-import ctypes
-
 import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
 
 from ldl_reference import local_variance64, reference64
+from raw_loss import RawLoss, replays_as_hip_graph, side_stream_equals_default_stream
 from test_cpu_ldl import restated_loss, restated_map
 
 pytestmark = pytest.mark.gpu
@@ -418,67 +417,30 @@ def test_local_weights_on_a_residual_with_a_mean(shape, k, mean):
 
 
 # ----------------------------------------------------------------------------------- streams and graphs (C ABI) ----
-class _RawLoss:
-    """ssg_ldl_loss through the C ABI with preallocated loss / grad / workspace, on torch's current stream."""
-
-    def __init__(self, shape, k=7):
-        from ssl_amd import _lib
-        self.L, self.shape, self.k = _lib.lib(), shape, k
-        B, C, H, W = shape
-        self.nb = self.L.ssg_ldl_workspace_bytes(B, H, W)
-        self.ws = torch.empty(self.nb, dtype=torch.uint8, device=DEV)
-        self.loss = torch.zeros(1, device=DEV)
-        self.grad = torch.zeros(shape, device=DEV)
-
-    def __call__(self, o, g, e):
-        B, C, H, W = self.shape
-        rc = self.L.ssg_ldl_loss(o.data_ptr(), g.data_ptr(), e.data_ptr(), B, C, H, W, self.k, 1.0, 1,
-                                 self.loss.data_ptr(), self.grad.data_ptr(), self.ws.data_ptr(), self.nb,
-                                 ctypes.c_void_p(torch.cuda.current_stream().cuda_stream))
-        assert rc == 0, rc
+def _raw_loss(shape, k=7):
+    """ssg_ldl_loss through the C ABI (raw_loss.RawLoss): loss and grad."""
+    from ssl_amd import _lib
+    B, C, H, W = shape
+    L = _lib.lib()
+    return RawLoss(L.ssg_ldl_loss, L.ssg_ldl_workspace_bytes(B, H, W),
+                   lambda o, g, e: (o.data_ptr(), g.data_ptr(), e.data_ptr(), B, C, H, W, k, 1.0, 1),
+                   (torch.zeros(1, device=DEV), torch.zeros(shape, device=DEV)))
 
 
 def test_side_stream_equals_default_stream():
     """Three launches in a line on the caller's stream; fixed-order sums: the same bits on any stream."""
     shape = (4, 3, 96, 80)
     o, g, e = _inputs(shape, 41)
-    a, b = _RawLoss(shape), _RawLoss(shape)
-    a(o, g, e)
-    torch.cuda.synchronize()
-    side = torch.cuda.Stream()
-    side.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(side):
-        b(o, g, e)
-    side.synchronize()
+    a = side_stream_equals_default_stream(lambda: _raw_loss(shape), (o, g, e))
     loss, grad = _hip(o, g, e, 7)
-    assert torch.equal(a.loss, b.loss) and torch.equal(a.grad, b.grad)
     assert torch.equal(a.loss[0], loss) and torch.equal(a.grad, grad)
 
 
 def test_loss_replays_as_hip_graph():
-    """One eager call, then the same call captured once and replayed after the inputs were overwritten in place: every
-    replay equals the eager result for the batch then in the buffers, bit for bit (the pattern of
-    test_gpu_tiny.py::test_tiny_step_replays_as_hip_graph)."""
+    """Three batches: the second one replayed twice."""
     shape = (4, 3, 96, 80)
     first, second = _inputs(shape, 51), _inputs(shape, 52, kind="unclamped")
-    o, g, e = (t.clone() for t in first)
-    eager, rec = _RawLoss(shape), _RawLoss(shape)
-    eager(o, g, e)
-    torch.cuda.synchronize()
-    graph = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(graph):
-        rec(o, g, e)
-    for batch in (first, second, second):
-        for dst, src in zip((o, g, e), batch):
-            dst.copy_(src)
-        eager(o, g, e)
-        torch.cuda.synchronize()
-        want = eager.loss.clone(), eager.grad.clone()
-        rec.loss.zero_()
-        rec.grad.zero_()
-        graph.replay()
-        torch.cuda.synchronize()
-        assert torch.equal(rec.loss, want[0]) and torch.equal(rec.grad, want[1])
+    want = replays_as_hip_graph(lambda: _raw_loss(shape), (first, second, second))
     assert not torch.equal(want[1], _hip(*first, 7)[1])      # the second batch really differs
 
 
