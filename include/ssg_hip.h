@@ -65,6 +65,7 @@ typedef void *ssg_stream_t; /* hipStream_t */
  * (LDL's artifact map, section (F)); nothing existing changed, so the version number stays. */
 /* 6, additive: + ssg_bbl_workspace_bytes, ssg_bbl_search, ssg_bbl_loss, ssg_flat_mask (BebyGAN's best-buddy loss and
  * flat mask, section (G)); again nothing existing changed. */
+/* 6, additive: + ssg_synth_kernels and its record (the degradation chain's blur and sinc kernels, section (I)). */
 int ssg_abi_version(void);
 const char *ssg_status_string(int status);
 /* Device-side refusals that no return value can carry (everything is asynchronous): waits for `stream`, then returns
@@ -556,6 +557,43 @@ int ssg_bp_downsample_backward(const float *grad_y, int planes, int H, int W, in
 int ssg_bp_loss(const float *x, const float *lq, int planes, int H, int W, int s, float loss_weight, int mean,
                 float *loss_out, float *grad_x /* nullable */, float *y_out /* nullable */, void *workspace,
                 size_t workspace_bytes, ssg_stream_t stream);
+
+/* ---------------------------------------------------------------- (I) ----
+ * The kernels the degradation chain convolves with (the dataset's per-sample kernel synthesis,
+ * basicsr/data/my_realesrgan_image_mask_dataset.py:88-141 through basicsr/data/degradations.py:16-173,389-409),
+ * ssl_amd/csrc/ssg_kernels.hip.  One record describes one K x K kernel, K = size:
+ *   SSG_KERNEL_PULSE        1 at the centre, 0 elsewhere (the dataset's pulse_tensor)
+ *   SSG_KERNEL_SINC         circular_lowpass_kernel: omega_c J1(omega_c r) / (2 pi r), r the distance from
+ *                           ((K-1)/2, (K-1)/2); omega_c^2 / (4 pi) at the centre
+ *   SSG_KERNEL_GAUSSIAN     bivariate_Gaussian: exp(-q / 2)
+ *   SSG_KERNEL_GENERALIZED  bivariate_generalized_Gaussian: exp(-q^beta / 2)
+ *   SSG_KERNEL_PLATEAU      bivariate_plateau: 1 / (q^beta + 1)
+ * with q = g^T Sigma^-1 g on the grid g = (x, y), x, y in -(K/2) .. K/2, x along columns (mesh_grid), Sigma =
+ * U diag(sig_x^2, sig_y^2) U^T, U the rotation by theta (sigma_matrix2; an isotropic kernel is sig_y = sig_x, theta =
+ * 0).  Every kind but the pulse is divided by the sum of its K^2 values; the kernel then sits centred in a pad_to x
+ * pad_to square of zeros at offset (pad_to - K) / 2 (the dataset's np.pad).  All arithmetic is fp64, Sigma's inverse
+ * and the sum included; the one fp32 rounding is the store, so an element differs from the reference's
+ * torch.FloatTensor(kernel) by one fp32 ulp at most.  Fields a kind does not use are ignored.
+ *
+ * ssg_synth_kernels: `records` are n records in HOST memory; they are checked, copied to `records_dev` (n records of
+ * device memory, scratch) by one asynchronous copy on `stream` and expanded by one launch into out (n, pad_to, pad_to)
+ * fp32, of which every element is written, the zeros included (out needs no clearing).  One workgroup per kernel, a
+ * fixed-order sum, no atomics: bit-reproducible.  `records` may be released when the call has returned if it is
+ * pageable memory (the runtime has staged it by then), and once the copy has completed on `stream` if it is pinned.
+ * Status, decided before the copy and the launch: SSG_E_BADARG for n < 0, pad_to even, < 1 or > 21, a null pointer, a
+ * record whose size is even, < 1 or > pad_to, or an unknown kind; n == 0 succeeds and does nothing. */
+#define SSG_KERNEL_PULSE 0
+#define SSG_KERNEL_SINC 1
+#define SSG_KERNEL_GAUSSIAN 2
+#define SSG_KERNEL_GENERALIZED 3
+#define SSG_KERNEL_PLATEAU 4
+typedef struct ssg_kernel_record {
+  int32_t kind;   /* SSG_KERNEL_* */
+  int32_t size;   /* K, odd, <= pad_to */
+  double sig_x, sig_y, theta, beta, omega_c;
+} ssg_kernel_record;   /* 48 bytes */
+int ssg_synth_kernels(const ssg_kernel_record *records, int n, int pad_to, ssg_kernel_record *records_dev, float *out,
+                      ssg_stream_t stream);
 
 #ifdef SSG_PROFILE
 /* PROFILING BUILD ONLY (libssg_hip_prof.so, compiled with -DSSG_PROFILE; the product library libssg_hip.so does not

@@ -62,6 +62,7 @@ PROTOTYPES = {
     "ssg_poisson_scratch_bytes": (_sz, [_i]),
     "ssg_poisson_rates": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "ssg_poisson_noise": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
+    "ssg_synth_kernels": (_i, [_vp, _i, _i, _vp, _vp, _vp]),
     "ssg_kernel_name": (ctypes.c_char_p, [_i, _i, _i]),
     "ssg_ldl_workspace_bytes": (_sz, [_i, _i, _i]),
     "ssg_artifact_map": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _sz, _vp]),

@@ -1241,6 +1241,22 @@ int ssg_filter2d(const float *img, const float *kernels, float *out, int B, int 
   return rc == -1 ? SSG_E_BADARG : rc == -4 ? SSG_E_IMAGESMALL : rc;
 }
 
+int ssg_synth_kernels(const ssg_kernel_record *records, int n, int pad_to, ssg_kernel_record *records_dev, float *out,
+                      ssg_stream_t stream) {
+  if (n < 0 || pad_to < 1 || pad_to > SYNTH_MAX_PAD || !(pad_to & 1)) return SSG_E_BADARG;
+  if (n == 0) return 0;
+  if (!records || !records_dev || !out) return SSG_E_BADARG;
+  for (int i = 0; i < n; ++i) {
+    const ssg_kernel_record &r = records[i];
+    if (r.kind < SSG_KERNEL_PULSE || r.kind > SSG_KERNEL_PLATEAU) return SSG_E_BADARG;
+    if (r.size < 1 || !(r.size & 1) || r.size > pad_to) return SSG_E_BADARG;
+  }
+  const int rc = (int)hipMemcpyAsync(records_dev, records, (size_t)n * sizeof(ssg_kernel_record), hipMemcpyHostToDevice,
+                                     (hipStream_t)stream);
+  if (rc) return rc;
+  return launch_synth_kernels(records_dev, n, pad_to, out, (hipStream_t)stream);
+}
+
 int ssg_diffjpeg(const float *img, float *out, int B, int H, int W, const float *quality_dev, float quality,
                  ssg_stream_t stream) {
   if (B < 0 || H <= 0 || W <= 0) return SSG_E_BADARG;

@@ -3,6 +3,8 @@
 // whose signature drifts from its declaration no longer compiles instead of becoming a new overload and an undefined
 // symbol when the library is loaded.  The parameter structs live in ssg_common.hpp.
 #pragma once
+#include "../../include/ssg_hip.h"
+
 #include "ssg_common.hpp"
 
 namespace ssg {
@@ -98,6 +100,10 @@ int launch_filter2d(const float *img, const float *kernels, float *out, int B, i
                     hipStream_t st);
 int launch_jpeg(const float *img, float *out, int B, int H, int W, const float *quality_dev, float quality_host,
                 hipStream_t st);
+
+// ---- ssg_kernels.hip: the degradation chain's blur / sinc / pulse kernels from their parameter records ----
+constexpr int SYNTH_MAX_PAD = 21;   // the largest padded kernel (stock Real-ESRGAN's; filter2d's largest k)
+int launch_synth_kernels(const ssg_kernel_record *records_dev, int n, int pad_to, float *out, hipStream_t st);
 
 // ---- ssg_api.hip ----
 // host-mapped {rows for the direct kernels, dense tiles} of the device's last plan, written by the edge-list builder's

@@ -8,11 +8,18 @@
                   :339-341): the queue is never permuted in memory -- the reference's `queue[idx]` shuffle is a slot
                   table here -- and a step moves only the b samples that change places (ssg_pool_swap).
 
+`draw_kernels` / `synth_kernels` = the dataset's per-sample blur, sinc and pulse kernels
+                  (basicsr/data/my_realesrgan_image_mask_dataset.py:88-141 through basicsr/data/degradations.py:16-173,
+                  324-409): the draws on the host, the kernels of a whole batch in one launch (ssg_synth_kernels).
+
 Random draws follow the reference call by call (python `random` for flips / crop origin, `torch.randperm` for the
 pool), so a run seeded like the reference's produces the same batches.  Byte moves only: results are bit exact.
 """
+import math
 import random
+from collections import namedtuple
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -364,6 +371,147 @@ def random_add_poisson_noise(img, scale_range, gray_prob, draws, clip=True, roun
     return add_poisson_noise(img, scale, gray, vals, dc, dg, clip, rounds)
 
 
+# ------------------------------------------------------------------ the kernels the chain convolves with ----
+KERNEL_KINDS = {"pulse": 0, "sinc": 1, "gaussian": 2, "generalized": 3, "plateau": 4}      # SSG_KERNEL_* of ssg_hip.h
+# one kernel's parameters (ssg_kernel_record): kind a name of KERNEL_KINDS, size K (odd); an isotropic kernel is
+# sig_y = sig_x with theta = 0; fields a kind does not use stay 0
+KernelRecord = namedtuple("KernelRecord", "kind size sig_x sig_y theta beta omega_c", defaults=(0.0,) * 5)
+_RECORD_DTYPE = np.dtype([("kind", "<i4"), ("size", "<i4"), ("sig_x", "<f8"), ("sig_y", "<f8"), ("theta", "<f8"),
+                          ("beta", "<f8"), ("omega_c", "<f8")], align=True)
+assert _RECORD_DTYPE.itemsize == 48
+
+
+def pack_records(records):
+    """KernelRecords -> the C ABI's array of ssg_kernel_record (a numpy structured array in host memory)."""
+    arr = np.zeros(len(records), dtype=_RECORD_DTYPE)
+    for i, r in enumerate(records):
+        if r.kind not in KERNEL_KINDS:
+            raise ValueError(f"ssl_amd.datapath: unknown kernel kind {r.kind!r} (one of {sorted(KERNEL_KINDS)})")
+        arr[i] = (KERNEL_KINDS[r.kind], int(r.size)) + tuple(float(v) for v in r[2:])
+    return arr
+
+
+@torch.no_grad()
+def synth_kernels(records, pad_to, device=None):
+    """KernelRecords -> (n, pad_to, pad_to) float32 on the GPU: each kernel evaluated in fp64, normalised, centred in
+    the pad_to square (odd, <= 21) and rounded once.  One host-to-device copy of the records, one launch."""
+    device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    if device.type != "cuda":
+        raise RuntimeError("ssl_amd.datapath.synth_kernels: the kernels are made on the GPU (there is no CPU path)")
+    host = pack_records(records)
+    n = len(host)
+    out = torch.empty((n, int(pad_to), int(pad_to)), dtype=torch.float32, device=device)
+    staged = torch.empty(max(n, 1) * _RECORD_DTYPE.itemsize, dtype=torch.uint8, device=device)
+    with torch.cuda.device(device):
+        _lib.check(_lib.lib().ssg_synth_kernels(host.ctypes.data, n, int(pad_to), _ptr(staged), _ptr(out), _stream()))
+    return out
+
+
+def _no_grid(grid):
+    if grid is not None:
+        raise NotImplementedError("ssl_amd.datapath: the kernel grid is the reference's mesh_grid(kernel_size); "
+                                  "a caller's grid= is not supported")
+
+
+def _sigmas(sig_x, sig_y, theta, isotropic):
+    return (sig_x, sig_x, 0.0) if isotropic else (sig_x, sig_y, theta)       # degradations.py:103-106
+
+
+def circular_lowpass_kernel(cutoff, kernel_size, pad_to=0, device=None):
+    """degradations.py:389-409 (the 2-D sinc filter): (max(kernel_size, pad_to),) * 2 float32 on the GPU."""
+    rec = KernelRecord("sinc", kernel_size, omega_c=cutoff)
+    return synth_kernels([rec], pad_to if pad_to > kernel_size else kernel_size, device)[0]
+
+
+def bivariate_Gaussian(kernel_size, sig_x, sig_y, theta, grid=None, isotropic=True, device=None):
+    """degradations.py:84-109."""
+    _no_grid(grid)
+    return synth_kernels([KernelRecord("gaussian", kernel_size, *_sigmas(sig_x, sig_y, theta, isotropic))],
+                         kernel_size, device)[0]
+
+
+def bivariate_generalized_Gaussian(kernel_size, sig_x, sig_y, theta, beta, grid=None, isotropic=True, device=None):
+    """degradations.py:112-140."""
+    _no_grid(grid)
+    return synth_kernels([KernelRecord("generalized", kernel_size, *_sigmas(sig_x, sig_y, theta, isotropic), beta)],
+                         kernel_size, device)[0]
+
+
+def bivariate_plateau(kernel_size, sig_x, sig_y, theta, beta, grid=None, isotropic=True, device=None):
+    """degradations.py:143-173."""
+    _no_grid(grid)
+    return synth_kernels([KernelRecord("plateau", kernel_size, *_sigmas(sig_x, sig_y, theta, isotropic), beta)],
+                         kernel_size, device)[0]
+
+
+_MIXED_KINDS = {"iso": ("gaussian", True), "aniso": ("gaussian", False), "generalized_iso": ("generalized", True),
+                "generalized_aniso": ("generalized", False), "plateau_iso": ("plateau", True),
+                "plateau_aniso": ("plateau", False)}
+
+
+def draw_mixed_kernel(kernel_list, kernel_prob, kernel_size=21, sigma_x_range=(0.6, 5), sigma_y_range=(0.6, 5),
+                      rotation_range=(-math.pi, math.pi), betag_range=(0.5, 8), betap_range=(0.5, 8), draws=None):
+    """The draws of random_mixed_kernels (degradations.py:324-383 with the random_bivariate_* it calls, :176-321) as a
+    KernelRecord: the kind, sig_x, [sig_y, rotation for the *aniso kinds], [which side of 1, then beta, for the
+    generalized and plateau kinds]."""
+    d = draws if draws is not None else Draws()
+    name = d.choices(kernel_list, kernel_prob)
+    if name not in _MIXED_KINDS:
+        raise NotImplementedError(f"ssl_amd.datapath: kernel type {name!r} (the reference has code for "
+                                  f"{sorted(_MIXED_KINDS)})")
+    kind, isotropic = _MIXED_KINDS[name]
+    sig_x = d.uniform(sigma_x_range[0], sigma_x_range[1])
+    sig_y, theta = sig_x, 0.0
+    if not isotropic:
+        sig_y = d.uniform(sigma_y_range[0], sigma_y_range[1])
+        theta = d.uniform(rotation_range[0], rotation_range[1])
+    beta = 0.0
+    if kind != "gaussian":
+        lo, hi = betag_range if kind == "generalized" else betap_range
+        beta = d.uniform(lo, 1) if d.uniform() < 0.5 else d.uniform(1, hi)
+    return KernelRecord(kind, kernel_size, sig_x, sig_y, theta, beta)
+
+
+def random_mixed_kernels(kernel_list, kernel_prob, kernel_size=21, sigma_x_range=(0.6, 5), sigma_y_range=(0.6, 5),
+                         rotation_range=(-math.pi, math.pi), betag_range=(0.5, 8), betap_range=(0.5, 8),
+                         noise_range=None, device=None):
+    """degradations.py:324-383: one randomly drawn (kernel_size,) * 2 blur kernel, float32 on the GPU."""
+    if noise_range is not None:
+        raise NotImplementedError("ssl_amd.datapath.random_mixed_kernels: multiplicative kernel noise (noise_range) is "
+                                  "not built; the dataset passes None")
+    rec = draw_mixed_kernel(kernel_list, kernel_prob, kernel_size, sigma_x_range, sigma_y_range, rotation_range,
+                            betag_range, betap_range)
+    return synth_kernels([rec], kernel_size, device)[0]
+
+
+def draw_kernels(dataset_opt, draws=None, pad_to=9):
+    """(kernel1, kernel2, sinc_kernel) of one sample as KernelRecords: the draws of
+    my_realesrgan_image_mask_dataset.py:89-141 in that order and from the same generators.  `dataset_opt` is the
+    dataset's option dict (opt['datasets']['train']); `pad_to` the padded size the kernels will be given -- 9, which
+    this fork's dataset hard-codes (:108,131,138), up to stock Real-ESRGAN's 21."""
+    o, d = dataset_opt, draws if draws is not None else Draws()
+    out = []
+    for sfx in ("", "2"):
+        lo, hi = o["blur_kernel_size_min" + sfx], o["blur_kernel_size_max" + sfx]
+        sizes = [2 * v + 1 for v in range(lo, hi + 1)]                                    # kernel_range[2], :63-65
+        if max(sizes) > pad_to:
+            raise ValueError(f"blur_kernel_size_max{sfx} gives kernels of {max(sizes)}, larger than the padded size "
+                             f"{pad_to}")
+        k = d.choice(sizes)
+        if d.uniform() < o["sinc_prob" + sfx]:
+            out.append(KernelRecord("sinc", k, omega_c=d.uniform(math.pi / 3 if k < 13 else math.pi / 5, math.pi)))
+        else:
+            out.append(draw_mixed_kernel(o["kernel_list" + sfx], o["kernel_prob" + sfx], k, o["blur_sigma" + sfx],
+                                         o["blur_sigma" + sfx], [-math.pi, math.pi], o["betag_range" + sfx],
+                                         o["betap_range" + sfx], d))
+    if d.uniform() < o["final_sinc_prob"]:
+        k = d.choice(sizes)                      # (kernel_range2, :136)
+        out.append(KernelRecord("sinc", k, omega_c=d.uniform(math.pi / 3, math.pi)))
+    else:
+        out.append(KernelRecord("pulse", 1))
+    return tuple(out)
+
+
 class Degradation:
     """`RealESRGANSSLModel.feed_data` (basicsr/models/realesrganssl_model.py:148-316) on the GPU: USM sharpening, the
     one- or two-stage degradation chain (blur, random resize, Gaussian / Poisson noise, JPEG, [resize back + sinc]),
@@ -372,11 +520,14 @@ class Degradation:
     reads); `draws` supplies the random choices (default: the reference's generators).
 
     feed(data) takes the dataloader's dict (gt, gt_mask, kernel1, kernel2, sinc_kernel on the GPU) and returns
-    dict(lq, gt, gt_usm | None, gt_mask)."""
+    dict(lq, gt, gt_usm | None, gt_mask).  A dict with none of the three kernels gets them made here, as the dataset
+    makes them: the draws of draw_kernels per sample from opt['datasets']['train'], before any other draw of the
+    step, then all 3 B kernels in one launch, padded to `kernel_pad_to`."""
 
-    def __init__(self, opt, draws=None):
+    def __init__(self, opt, draws=None, kernel_pad_to=9):
         self.opt = opt
         self.draws = draws if draws is not None else Draws()
+        self.kernel_pad_to = kernel_pad_to
         self.jpeger = DiffJPEG(differentiable=False)
         self.usm_sharpener = USMSharp()
         self.pool = PairPool(opt["queue_size"]) if opt.get("queue_size") else None
@@ -411,6 +562,14 @@ class Degradation:
         opt, d = self.opt, self.draws
         gt, gt_mask = data['gt'], data['gt_mask']
         _need_gpu(gt, gt_mask)
+        given = [k for k in ('kernel1', 'kernel2', 'sinc_kernel') if k in data]
+        if not given:
+            B = gt.shape[0]
+            recs = [draw_kernels(opt['datasets']['train'], d, self.kernel_pad_to) for _ in range(B)]
+            made = synth_kernels([r[j] for j in range(3) for r in recs], self.kernel_pad_to, gt.device)
+            data = dict(data, kernel1=made[:B], kernel2=made[B:2 * B], sinc_kernel=made[2 * B:])
+        elif len(given) != 3:
+            raise ValueError(f"feed needs kernel1, kernel2 and sinc_kernel together or none of them (got {given})")
         sharpen = opt.get('Use_sharpen', None) is not None
         gt_usm = self.usm_sharpener(gt) if sharpen else None
         ori_h, ori_w = gt.shape[2:4]
