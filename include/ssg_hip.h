@@ -595,6 +595,44 @@ typedef struct ssg_kernel_record {
 int ssg_synth_kernels(const ssg_kernel_record *records, int n, int pad_to, ssg_kernel_record *records_dev, float *out,
                       ssg_stream_t stream);
 
+/* ---------------------------------------------------------------- (J) ----
+ * The validation metrics (basicsr/metrics/psnr_ssim.py: calculate_psnr, calculate_ssim on what tensor2img,
+ * basicsr/utils/img_util.py:37-93, hands them; to_y_channel and bgr2ycbcr in between), ssl_amd/csrc/ssg_metrics.hip.
+ * Two images of one shape come in, one row of results per image goes out; nothing is copied to the host.
+ *   kind      SSG_METRIC_F32_RGB  fp32 planar (B,C,H,W), RGB, nominal [0, 1] (a model's tensors): quantised as
+ *                                 q = rint(fl32(clamp(x, 0, 1) * 255.0f)), ties to even, and read in BGR order
+ *             SSG_METRIC_U8_HWC   uint8 interleaved (B,H,W,C), BGR (a decoded image file)
+ *             SSG_METRIC_U8_CHW   uint8 planar (B,C,H,W), BGR
+ *   crop      crop_border pixels from each side; 0 = none
+ *   planes    y_channel != 0, C = 3: v_c = fl32(q_c / 255.0f); t = ((24.966 v_b + 128.553 v_g) + 65.481 v_r) + 16.0
+ *             in fp64 without fma; the one plane is fl32(fl32(t / 255.0) * 255.0f).  y_channel != 0, C = 1:
+ *             fl32(fl32(q / 255.0f) * 255.0f).  y_channel == 0: the C planes are the integers q, in BGR order.
+ *   PSNR      10 log10(255^2 / mse), mse the fp64 mean of the squared plane differences over planes and pixels (summed
+ *             in integers, exactly, when y_channel == 0); +inf where mse == 0
+ *   SSIM      per plane the five moments under the 11 x 11 Gaussian window (sigma 1.5) on the 'valid' region
+ *             (H - 2 crop - 10) x (W - 2 crop - 10), c1 = (0.01 * 255)^2, c2 = (0.03 * 255)^2, the map
+ *             ((2 mu1 mu2 + c1)(2 s12 + c2)) / ((mu1^2 + mu2^2 + c1)(s1 + s2 + c2)), its mean over map and planes; fp64
+ * A NaN in a float input is unspecified (the reference's uint8 cast of NaN is undefined).
+ * Status, decided before any launch with the outputs untouched: SSG_E_BADARG for a null pointer, B, H or W <= 0, C not
+ * 1 or 3, crop_border < 0 or an unknown kind; SSG_E_TOOLARGE for B > 65535 or 2^31 elements and more;
+ * SSG_E_IMAGESMALL for a cropped side shorter than 11 (the reference would return the mean of an empty map; for the
+ * planes alone: shorter than 1); SSG_E_WORKSPACE for workspace_bytes < the size reported for the shape (which is 0 for
+ * a shape outside the domain; it holds at most 512 partial sums of three kinds per image: 12 KiB per image + 768 bytes
+ * at most, nothing of image size); SSG_E_ALIGN for a workspace that is not 16-byte aligned.
+ * No atomics, fixed summation orders (bit-reproducible), no allocation, synchronisation or host read.
+ * ssg_psnr_ssim: out (B,4) fp64 on the device: PSNR, SSIM, the sum of the squared plane differences, the number of
+ *   values in that sum.  Two launches.
+ * ssg_metric_planes: planes_out (B,P,H - 2 crop,W - 2 crop) fp32, P = 1 with y_channel and C otherwise: the planes
+ *   the metrics are computed on.  One launch. */
+#define SSG_METRIC_F32_RGB 0
+#define SSG_METRIC_U8_HWC 1
+#define SSG_METRIC_U8_CHW 2
+size_t ssg_metric_workspace_bytes(int B, int C, int H, int W, int crop_border);
+int ssg_psnr_ssim(const void *a, const void *b, int kind, int B, int C, int H, int W, int crop_border, int y_channel,
+                  double *out, void *workspace, size_t workspace_bytes, ssg_stream_t stream);
+int ssg_metric_planes(const void *img, int kind, int B, int C, int H, int W, int crop_border, int y_channel,
+                      float *planes_out, ssg_stream_t stream);
+
 #ifdef SSG_PROFILE
 /* PROFILING BUILD ONLY (libssg_hip_prof.so, compiled with -DSSG_PROFILE; the product library libssg_hip.so does not
  * export this symbol and has no code path that skips work).  Results are WRONG while a mask is set: skip kernel

@@ -105,6 +105,9 @@ int launch_jpeg(const float *img, float *out, int B, int H, int W, const float *
 constexpr int SYNTH_MAX_PAD = 21;   // the largest padded kernel (stock Real-ESRGAN's; filter2d's largest k)
 int launch_synth_kernels(const ssg_kernel_record *records_dev, int n, int pad_to, float *out, hipStream_t st);
 
+// ---- ssg_metrics.hip: PSNR / SSIM (its entry points are defined beside its kernels) ----
+size_t metric_workspace_bytes(int B, int C, int H, int W, int crop);
+
 // ---- ssg_api.hip ----
 // host-mapped {rows for the direct kernels, dense tiles} of the device's last plan, written by the edge-list builder's
 // scan kernel (nullptr: no hint wanted, or none allocated yet and `st` is being captured)

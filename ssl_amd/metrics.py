@@ -1,0 +1,185 @@
+"""PSNR and SSIM as the reference's validation loop computes them, on the GPU (ssl_amd/csrc/ssg_metrics.hip).
+
+Named as `basicsr.metrics` names them: `calculate_psnr`, `calculate_ssim` and `calculate_metric` keep the reference's
+signatures, its ValueError and its shape assertion; `psnr_ssim` is the batched call on a model's own tensors (what
+`tensor2img` + `calculate_metric` do per image, without leaving the device), `MetricAverager` the validation loop's
+`metric_results[name] += ...; metric_results[name] /= idx + 1` with one synchronisation at the end.
+
+Contract: include/ssg_hip.h section (J).  A NaN in a float input is unspecified, as in the reference.  An image whose
+cropped side is shorter than 11 is refused (the reference's SSIM would be the mean of an empty map); there is no CPU
+path."""
+from copy import deepcopy
+
+import numpy as np
+import torch
+
+from . import _lib
+from .engine import _launch, _need_gpu, _ptr, _workspace
+
+__all__ = ["calculate_psnr", "calculate_ssim", "calculate_metric", "psnr_ssim", "MetricAverager"]
+
+KIND_F32_RGB, KIND_U8_HWC, KIND_U8_CHW = 0, 1, 2
+
+
+def _device():
+    return torch.device("cuda", torch.cuda.current_device())
+
+
+def _run(a, b, kind, B, C, H, W, crop_border, y_channel):
+    """(B,4) float64 on the device: PSNR, SSIM, the sum of squared plane differences, its number of terms."""
+    _need_gpu(a, b)
+    L = _lib.lib()
+    out = torch.empty((B, 4), dtype=torch.float64, device=a.device)
+    ws, nb = _workspace(L.ssg_metric_workspace_bytes(B, C, H, W, int(crop_border)), a.device)
+    _launch(a.device, L.ssg_psnr_ssim, _ptr(a), _ptr(b), kind, B, C, H, W, int(crop_border), int(bool(y_channel)),
+            _ptr(out), _ptr(ws), nb)
+    return out
+
+
+def metric_planes(img, kind, crop_border=0, test_y_channel=False):
+    """The float32 planes (B,P,Hc,Wc) the metrics are computed on, after quantise, crop and Y: `img` is a contiguous
+    device tensor laid out as `kind` says ((B,C,H,W), or (B,H,W,C) for KIND_U8_HWC)."""
+    _need_gpu(img)
+    if kind == KIND_U8_HWC:
+        B, H, W, C = img.shape
+    else:
+        B, C, H, W = img.shape
+    P = 1 if test_y_channel else C
+    out = torch.empty((B, P, max(H - 2 * crop_border, 0), max(W - 2 * crop_border, 0)), dtype=torch.float32,
+                      device=img.device)
+    _launch(img.device, _lib.lib().ssg_metric_planes, _ptr(img.contiguous()), kind, B, C, H, W, int(crop_border),
+            int(bool(test_y_channel)), _ptr(out))
+    return out
+
+
+def psnr_ssim(sr, gt, crop_border=0, test_y_channel=False):
+    """PSNR and SSIM of float (N,C,H,W) (or (C,H,W)) RGB tensors in nominal [0, 1], as `visuals['result']` and
+    `visuals['gt']` hold them: what the reference gets from tensor2img (clamp, * 255, round half to even, uint8, BGR)
+    followed by calculate_psnr / calculate_ssim.  Returns a device (N,2) float64 tensor {PSNR, SSIM}; runs on the
+    current stream without synchronising with the host."""
+    assert sr.shape == gt.shape, (f'Image shapes are different: {sr.shape}, {gt.shape}.')
+    if not (torch.is_tensor(sr) and sr.is_floating_point() and gt.is_floating_point()):
+        raise TypeError("ssl_amd: psnr_ssim takes floating-point tensors (use calculate_psnr / calculate_ssim for "
+                        "uint8 images)")
+    if sr.dim() == 3:
+        sr, gt = sr[None], gt[None]
+    if sr.dim() != 4:
+        raise ValueError(f"ssl_amd: psnr_ssim takes (N,C,H,W) or (C,H,W) tensors, got {tuple(sr.shape)}")
+    dev = sr.device if sr.is_cuda else _device()       # host tensors are uploaded, as arrays are
+    a = sr.detach().to(device=dev, dtype=torch.float32).contiguous()
+    b = gt.detach().to(device=dev, dtype=torch.float32).contiguous()
+    B, C, H, W = a.shape
+    return _run(a, b, KIND_F32_RGB, B, C, H, W, crop_border, test_y_channel)[:, :2]
+
+
+def _as_image(img, input_order):
+    """A uint8 device tensor and its kind for an image in the reference's conventions: (H,W), (H,W,C) or (C,H,W), BGR,
+    uint8 or a float type holding the integers 0 .. 255 (the offline script's `img * 255`; rounded to the nearest)."""
+    t = torch.from_numpy(np.ascontiguousarray(img)) if isinstance(img, np.ndarray) else img
+    if not t.is_cuda:
+        t = t.to(_device())
+    if t.dtype != torch.uint8:
+        t = t.round().clamp(0, 255).to(torch.uint8)
+    if t.dim() == 2:
+        return t.contiguous()[None, None], KIND_U8_CHW
+    if t.dim() != 3:
+        raise ValueError(f"ssl_amd: an image is (H,W), (H,W,C) or (C,H,W), got {tuple(t.shape)}")
+    return t.contiguous()[None], (KIND_U8_CHW if input_order == 'CHW' else KIND_U8_HWC)
+
+
+def _both(img, img2, crop_border, input_order, test_y_channel):
+    assert img.shape == img2.shape, (f'Image shapes are different: {img.shape}, {img2.shape}.')
+    if input_order not in ['HWC', 'CHW']:
+        raise ValueError(f'Wrong input_order {input_order}. Supported input_orders are "HWC" and "CHW"')
+    a, kind = _as_image(img, input_order)
+    b, _ = _as_image(img2, input_order)
+    if kind == KIND_U8_HWC:
+        B, H, W, C = a.shape
+    else:
+        B, C, H, W = a.shape
+    return _run(a, b, kind, B, C, H, W, crop_border, test_y_channel)
+
+
+def calculate_psnr(img, img2, crop_border, input_order='HWC', test_y_channel=False, **kwargs):
+    """basicsr.metrics.calculate_psnr: images with range [0, 255], BGR, numpy arrays (uploaded) or tensors.  Returns a
+    Python float (inf for identical images)."""
+    return float(_both(img, img2, crop_border, input_order, test_y_channel)[0, 0])
+
+
+def calculate_ssim(img, img2, crop_border, input_order='HWC', test_y_channel=False, **kwargs):
+    """basicsr.metrics.calculate_ssim: as calculate_psnr."""
+    return float(_both(img, img2, crop_border, input_order, test_y_channel)[0, 1])
+
+
+_COLUMN = {"calculate_psnr": 0, "calculate_ssim": 1}
+
+
+def _column(metric_type):
+    if metric_type not in _COLUMN:
+        raise KeyError(f"No object named '{metric_type}' found in 'metric' registry!")
+    return _COLUMN[metric_type]
+
+
+def _is_model_tensor(x):
+    return torch.is_tensor(x) and x.is_floating_point()
+
+
+def calculate_metric(data, opt):
+    """basicsr.metrics.calculate_metric: dispatches on opt['type'].  Floating-point TENSORS in `data` (img=, img2=) are
+    taken for a model's (C,H,W) / (1,C,H,W) RGB tensors in [0, 1] and go through the quantising path, so a validation
+    loop can drop tensor2img; arrays and uint8 tensors are images as the reference passes them."""
+    opt = deepcopy(opt)
+    col = _column(opt.pop('type'))
+    img, img2 = data['img'], data['img2']
+    if _is_model_tensor(img) and _is_model_tensor(img2):
+        opt.pop('input_order', None)
+        out = psnr_ssim(img, img2, opt.get('crop_border', 0), opt.get('test_y_channel', False))
+        if out.shape[0] != 1:
+            raise ValueError("ssl_amd: calculate_metric takes one image per call (psnr_ssim is the batched call)")
+        return float(out[0, col])
+    return (calculate_psnr, calculate_ssim)[col](img, img2, **opt)
+
+
+class MetricAverager:
+    """The validation loop's running sums, kept on the device:
+
+        avg = MetricAverager()
+        for val_data in dataloader:                       # any image sizes
+            ...
+            avg.add_all(visuals['result'], visuals['gt'], opt['val']['metrics'])
+        metric_results = avg.result()                     # the one synchronisation
+
+    `add(name, sr, gt, **opt)` adds one metric (opt as in the YAML: type, crop_border, test_y_channel; type defaults
+    to 'calculate_' + name); `add_all` takes the YAML's whole `metrics` dict and runs the fused call once per distinct
+    (crop_border, test_y_channel).  `result()` returns {name: sum / images}: the reference's
+    metric_results[name] / (idx + 1)."""
+
+    def __init__(self):
+        self._sum = {}
+        self._count = {}
+
+    def _accumulate(self, name, values):
+        s = values.sum()
+        self._sum[name] = self._sum[name] + s if name in self._sum else s
+        self._count[name] = self._count.get(name, 0) + values.numel()
+
+    def add(self, name, sr, gt, **opt):
+        col = _column(opt.get('type', 'calculate_' + name))
+        out = psnr_ssim(sr, gt, opt.get('crop_border', 0), opt.get('test_y_channel', False))
+        self._accumulate(name, out[:, col])
+
+    def add_all(self, sr, gt, metrics):
+        done = {}
+        for name, opt in metrics.items():
+            col = _column(opt.get('type', 'calculate_' + name))
+            key = (int(opt.get('crop_border', 0)), bool(opt.get('test_y_channel', False)))
+            if key not in done:
+                done[key] = psnr_ssim(sr, gt, *key)
+            self._accumulate(name, done[key][:, col])
+
+    def result(self):
+        if not self._sum:
+            return {}
+        names = list(self._sum)
+        sums = torch.stack([self._sum[n] for n in names]).cpu().tolist()
+        return {n: s / self._count[n] for n, s in zip(names, sums)}
