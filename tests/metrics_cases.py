@@ -6,6 +6,8 @@ their size AFTER the crop; the kernel's map tile is 32 x 16 (W x H) and the map 
   11 x 11    one map pixel                     12 x 27    a partial tile
   27 x 43    one tile plus one on each axis    45 x 79    two tiles plus a remainder on each axis
   270 x 403  with 3 planes 17 x 13 x 3 = 663 tiles: more than the 512 workgroups an image gets, so a second trip
+  379 x 740  24 x 23 = 552 tiles in ONE plane, ragged on both axes: the second trip of a Y plane, where the fp64 sum of
+             squared differences is carried from a workgroup's first tile to its second
 """
 import collections
 import functools
@@ -105,6 +107,11 @@ def cases():
     add("identical", U8_HWC, 4, True, a, a.copy())
     a, _ = _noise(rng, 1, 20, 35, 3)
     add("identical_rgb_f32", F32_RGB, 0, False, layout(a, F32_RGB), layout(a, F32_RGB))
+    # past 512 tiles: in one Y plane (three channels, then grey), and with three different images in the batch, so that
+    # image i's partial sums lie at i * 512 in each of the workspace's three regions
+    noise("y_second_trip", U8_HWC, 2, 3, 379, 740, 4, True)
+    noise("grey_y_second_trip", U8_CHW, 1, 1, 379, 740, 0, True)
+    noise("batch_second_trip", F32_RGB, 3, 3, 270, 403, 0, False)
     return tuple(out)
 
 
@@ -115,6 +122,13 @@ def geometry(case):
     else:
         B, C, H, W = case.a.shape
     return B, C, H, W
+
+
+def tiles(case):
+    """The 32 x 16 map tiles of one image of a case: planes x tile rows x tile columns."""
+    _, C, H, W = geometry(case)
+    hm, wm = H - 2 * case.crop - 10, W - 2 * case.crop - 10
+    return (1 if case.y else C) * ((hm + 15) // 16) * ((wm + 31) // 32)
 
 
 @functools.lru_cache(maxsize=None)

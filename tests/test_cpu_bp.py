@@ -124,6 +124,29 @@ def test_bp_symbols_are_exported():
         assert 0 < nb <= 2 * P * (H // s) * (W // s) * 4 + 65536, (P, H, W, s)
 
 
+def test_trip_shapes_cross_the_forward_workgroup_cap():
+    """test_gpu_bp.TRIPS: the workspace behind the signs (one fp64 partial per forward workgroup) is the same for all
+    four shapes -- the cap -- and larger than at 16 x 3 x 192 x 192, and each shape has more 16 x 8 output tiles than
+    that.  Raising the cap fails here instead of sending the sweep back to one trip."""
+    from ssl_amd import _lib
+    from test_gpu_bp import TRIPS
+    L = _lib.lib()
+
+    def partials(s, shape):
+        B, C, H, W = shape
+        signs = -(-4 * B * C * (H // s) * (W // s) // 256) * 256
+        return L.ssg_bp_workspace_bytes(B * C, H, W, s) - signs
+
+    cap = {partials(s, shape) for s, shape in TRIPS}
+    assert len(TRIPS) == 4 and len(cap) == 1
+    cap = cap.pop()
+    assert cap > partials(4, (16, 3, 192, 192)) == 864 * 8
+    assert cap == partials(4, (100000, 3, 8, 8)) and cap % 8 == 0
+    for s, (B, C, H, W) in TRIPS:
+        tiles = B * C * -(-(H // s) // 8) * -(-(W // s) // 16)
+        assert tiles > cap // 8, (s, B, C, H, W, tiles)
+
+
 def test_bp_argument_checks_need_no_gpu():
     """SSG_E_BADARG (-1), SSG_E_TOOLARGE (-2), SSG_E_WORKSPACE (-3), SSG_E_IMAGESMALL (-4), SSG_E_ALIGN (-5): all
     decided before a launch (the pointers below are never dereferenced)."""

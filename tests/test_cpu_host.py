@@ -283,6 +283,22 @@ def test_argument_checks_need_no_gpu():
     assert L.ssg_backward_scratch_bytes(100, 25) >= 100 * 625 * 4
 
 
+def test_criteria_trip_sizes_cross_the_grid_caps():
+    """The sizes of test_gpu_ref_api's trip tests against the criteria grid read off the scratch size (two fp64 per
+    workgroup of the sums; the gradient runs four times as many): more 256-lane float4 workgroups than the grid has, by
+    less than one grid (a SECOND trip, lanes left over for the one-trip branch), and for the flush more than 32 float4
+    trips / 128 single-element trips per lane.  Raising a cap fails here instead of the tests going back to one trip."""
+    from ssl_amd import _lib
+    from test_gpu_ref_api import CRITERIA_FLUSH_N, CRITERIA_GRAD_TRIP_N, CRITERIA_SUMS_TRIP_N
+    grid = _lib.lib().ssg_criteria_scratch_bytes() // 16
+    assert _lib.lib().ssg_criteria_scratch_bytes() % 16 == 0
+    for n in (CRITERIA_SUMS_TRIP_N, CRITERIA_GRAD_TRIP_N, CRITERIA_FLUSH_N):
+        assert n / 4 / 256 > grid and n % 4 == 3
+    assert grid < CRITERIA_SUMS_TRIP_N / 4 / 256 < 2 * grid
+    assert 4 * grid < CRITERIA_GRAD_TRIP_N / 4 / 256 < 8 * grid
+    assert CRITERIA_FLUSH_N // 4 == 33 * grid * 256 and 128 * grid * 256 < CRITERIA_FLUSH_N - 1 < 256 * grid * 256
+
+
 def test_workspace_layout_of_the_fused_call():
     """ssg_loss_workspace_layout (host arithmetic only): the pieces lie in order inside ssg_loss_workspace_bytes(), the
     row-major scratch rows of the fused step behind them, and -- k_s = 49 only -- two tile-major regions of capacity / 128

@@ -190,6 +190,28 @@ def test_workspace_holds_partials_only():
     assert 3 * 512 * 8 < 2040 * 1356 // 64
 
 
+def test_second_trip_cases_cross_the_workgroup_cap():
+    """The cases named *_second_trip have more tiles than an image gets workgroups, the cap read off the size function
+    (its per-image share stops growing there): raising the cap fails here instead of sending them back to one trip."""
+    from ssl_amd import _lib
+    L = _lib.lib()
+    share = L.ssg_metric_workspace_bytes(1, 3, 4000, 4000, 0)
+    cap = share // (3 * 8)
+    assert share == L.ssg_metric_workspace_bytes(1, 3, 2040, 1356, 4) and share % (3 * 8) == 0
+    named = {c.name: c for c in MC.cases()}
+    for name in ("many_tiles_second_trip", "y_second_trip", "grey_y_second_trip", "batch_second_trip"):
+        assert MC.tiles(named[name]) > cap, (name, MC.tiles(named[name]), cap)
+    assert MC.tiles(named["y_second_trip"]) == MC.tiles(named["grey_y_second_trip"]) == 24 * 23
+    assert MC.tiles(named["cross_hwc_c3_y1_b3"]) < cap
+    # batch_second_trip: three images at the cap, no growth from its shape to a larger one
+    B, C, H, W = MC.geometry(named["batch_second_trip"])
+    assert (B, named["batch_second_trip"].y) == (3, False)
+    nb = L.ssg_metric_workspace_bytes(B, C, H, W, 0)
+    assert nb == B * share == L.ssg_metric_workspace_bytes(B, C, 2 * H, 2 * W, 0)
+    a = named["batch_second_trip"].a
+    assert not np.array_equal(a[0], a[1]) and not np.array_equal(a[1], a[2]) and not np.array_equal(a[0], a[2])
+
+
 # ---------------------------------------------------------------------------------------------- the offline tool ---
 def _load_tool():
     spec = importlib.util.spec_from_file_location("calculate_psnr_ssim_tool",

@@ -31,6 +31,9 @@ SWEEP = [(4, (2, 3, 48, 40)), (4, (1, 3, 50, 43)), (4, (1, 1, 6, 7)), (4, (1, 3,
          (4, (1, 3, 70, 67)), (4, (1, 3, 200, 136)), (4, (1, 2, 45, 83)),
          (3, (1, 3, 27, 31)), (3, (1, 3, 4, 5)), (3, (2, 3, 64, 47)),
          (2, (2, 1, 24, 26)), (2, (1, 3, 3, 4)), (2, (1, 3, 37, 90))]
+# more forward tiles (16 x 8 outputs each) than the 4,096 workgroups bp_fwd gets: a workgroup's second tile, and bp_bwd
+# folding 4,096 partial sums.  One-tile planes at s = 4, 3 and 2, then many ragged tiles per plane (33 x 28 on 6 planes)
+TRIPS = [(4, (1367, 3, 8, 9)), (3, (1366, 3, 7, 10)), (2, (1400, 3, 5, 6)), (2, (2, 3, 700, 650))]
 SMOOTH = [(4, (1, 3, 50, 43)), (3, (1, 3, 27, 31)), (2, (1, 3, 37, 90))]
 WEIGHTS = [('mean', 1.0), ('mean', 0.37), ('sum', 1.0), ('sum', 0.37)]
 
@@ -143,9 +146,12 @@ def test_hip_against_the_reference_fixture(golden):
 
 
 # ------------------------------------------------------------------------------------------------ the sweep ----
-@pytest.mark.parametrize("s,shape", SWEEP, ids=[f"s{s}-" + "x".join(map(str, sh)) for s, sh in SWEEP])
+@pytest.mark.parametrize("s,shape", SWEEP + TRIPS, ids=[f"s{s}-" + "x".join(map(str, sh)) for s, sh in SWEEP + TRIPS])
 def test_shape_sweep(s, shape):
-    check("sweep", s, shape)
+    if (s, shape) in TRIPS:      # (what these are for is the second trip, not the weights: one mean, one sum)
+        check("trips", s, shape, weights=WEIGHTS[:1] + WEIGHTS[3:])
+    else:
+        check("sweep", s, shape)
 
 
 @pytest.mark.parametrize("s,shape", SMOOTH, ids=[f"s{s}" for s, _ in SMOOTH])
@@ -287,7 +293,8 @@ def _dev_inputs(shape, s=4):
     return x.to(DEV), lq.to(DEV)
 
 
-@pytest.mark.parametrize("s,shape", [(4, (1, 3, 70, 67)), (4, (1, 3, 8, 9)), (3, (1, 3, 4, 5)), (2, (1, 3, 37, 90))])
+@pytest.mark.parametrize("s,shape", [(4, (1, 3, 70, 67)), (4, (1, 3, 8, 9)), (3, (1, 3, 4, 5)), (2, (1, 3, 37, 90)),
+                                     (4, (1367, 3, 8, 9))])
 def test_every_gradient_element_is_written(s, shape):
     """grad_x and y_out pre-filled with NaN: the call leaves none, and equals the Python layer bit for bit."""
     x, lq = _dev_inputs(shape, s)
@@ -347,10 +354,11 @@ def test_c_abi_refusals_on_the_device():
 def poison_cases():
     """What the LDS-poison test runs on the product build and again on the poisoned profiling build: the output, the
     generic backward, the loss and its gradient at the smallest sides, under both mirrors, at odd shapes of every
-    factor and past one tile on both axes."""
+    factor, past one tile on both axes and past one trip of the forward's 4,096 workgroups."""
     from ssl_amd import engine
     out = []
-    for s, shape in ((4, (1, 1, 6, 7)), (4, (1, 3, 8, 9)), (4, (1, 2, 45, 83)), (3, (2, 3, 64, 47)), (2, (1, 3, 37, 90))):
+    for s, shape in ((4, (1, 1, 6, 7)), (4, (1, 3, 8, 9)), (4, (1, 2, 45, 83)), (3, (2, 3, 64, 47)), (2, (1, 3, 37, 90)),
+                     (4, (1367, 3, 8, 9))):
         x, lq, g = (t.to(DEV) for t in inputs(s, shape))
         xs = x.clone().requires_grad_(True)
         y = engine.bp_downsample(xs, s)

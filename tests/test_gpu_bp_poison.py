@@ -18,7 +18,7 @@ def test_bp_kernels_under_lds_poison(word):
     want = tb.poison_cases()
     with poisoned(word):
         got = tb.poison_cases()
-    assert len(got) == len(want) == 20
+    assert len(got) == len(want) == 24
     for i, (a, b) in enumerate(zip(got, want)):
         assert bool(torch.isfinite(b.float()).all()), i
         assert torch.equal(a, b), (i, float((a.float() - b.float()).abs().max()))

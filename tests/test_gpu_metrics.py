@@ -1,8 +1,8 @@
 """The metric kernels (ssl_amd/csrc/ssg_metrics.hip) on the MI355X against the numpy restatement (metrics_reference.py)
 on the inputs of metrics_cases.py: the planes bit for bit, the squared-difference sums exactly (integers) or to the
 bound of a sum of N non-negative terms (Y), PSNR to 1e-12 dB of 10 log10 of those sums, SSIM to the restatement's derived
-bound; then determinism (repeat, side stream, HIP graph), the averager, the public functions on the fixture and the
-refusals with real device pointers."""
+bound; then metric_planes past one trip of its capped grid, determinism (repeat, side stream, HIP graph, whatever the
+workspace held), the averager, the public functions on the fixture and the refusals with real device pointers."""
 import ctypes
 import math
 
@@ -75,6 +75,29 @@ def test_psnr_ssim_against_restatement(index):
         assert err <= m["bound"], (ssim, m["ssim"], m["bound"])
         if case.name.startswith("identical"):
             assert ssim == 1.0
+
+
+def _plane_trip_inputs():
+    """Two inputs with more than 4,096 x 256 = 1,048,576 plane elements: metric_planes' grid is capped there and every
+    thread walks on by gridDim.x * 256.  Outside metrics_cases.cases(): no SSIM restatement is needed for the planes."""
+    rng = np.random.default_rng(4096)
+    q = rng.integers(0, 256, (3, 600, 600), dtype=np.uint8)                              # BGR planes
+    x = rng.random((3, 1032, 1032), dtype=np.float32) * np.float32(1.3) - np.float32(0.15)
+    return (("u8_chw_600", MC.U8_CHW, 0, False, q[None], R.planes(q.transpose(1, 2, 0), 0, False)),
+            ("f32_y_1032_crop1", MC.F32_RGB, 1, True, x[None], R.planes(R.quantise(x), 1, True)))
+
+
+@pytest.mark.parametrize("which", [0, 1], ids=["u8_chw_600", "f32_y_1032_crop1"])
+def test_planes_past_one_grid_trip(which):
+    from ssl_amd import metrics as M
+    name, kind, crop, y, img, want = _plane_trip_inputs()[which]
+    assert want.size > 4096 * 256
+    got = M.metric_planes(_dev(img), kind, crop, y).cpu()
+    want = torch.from_numpy(want[None])
+    assert got.dtype == torch.float32 and got.shape == want.shape
+    differing = int((got.view(torch.int32) != want.view(torch.int32)).sum())
+    print(f"TRIP planes {name}: {want.numel()} elements, {differing} differing")
+    assert differing == 0
 
 
 def test_fixture_through_public_functions(golden):
@@ -150,6 +173,24 @@ def test_repeat_and_side_stream_bit_equal(name):
         side_call(a, b)
     side.synchronize()
     assert torch.equal(first.out, side_call.out)
+
+
+@pytest.mark.parametrize("name", ["batch_second_trip", "cross_hwc_c3_y1_b3"])
+def test_result_ignores_what_the_workspace_held(name):
+    """Every partial the fold reads was written by this call's metric_tiles: a workspace of 0xFF bytes (NaN as fp64,
+    2^64 - 1 as a count) and one of zeros give the same bits, with 512 workgroups for 663 tiles and with one per tile."""
+    case = _named(name)
+    assert (MC.tiles(case) > 512) == (name == "batch_second_trip")
+    a, b = _dev(case.a), _dev(case.b)
+    outs = []
+    for byte in (0xFF, 0x00):
+        raw = Raw(case)
+        raw.ws.fill_(byte)
+        raw(a, b)
+        torch.cuda.synchronize()
+        outs.append(raw.out.clone())
+    assert bool(torch.isfinite(outs[0]).all())
+    assert torch.equal(outs[0].view(torch.int64), outs[1].view(torch.int64))
 
 
 def test_replays_as_hip_graph():
@@ -237,3 +278,19 @@ def test_refusals_leave_outputs_untouched():
         M.psnr_ssim(a, b, crop_border=11)
     with pytest.raises(RuntimeError):
         M.psnr_ssim(torch.rand((1, 2, 32, 32), device=DEV), torch.rand((1, 2, 32, 32), device=DEV))
+
+
+# ------------------------------------------------------------------ shared with test_gpu_metrics_poison.py ----
+def poison_cases():
+    """What the LDS-poison test runs on the product build and again on the poisoned profiling build: the raw (B,4)
+    results and both images' planes of one map pixel, one tile plus one on each axis, floats on Y, and the two kinds of
+    second trip (one Y plane; three planes and three images)."""
+    from ssl_amd import metrics as M
+    out = []
+    for name in ("one_map_pixel", "tile_plus_one", "floats_outside_unit", "y_second_trip", "batch_second_trip"):
+        case = _named(name)
+        a, b = _dev(case.a), _dev(case.b)
+        out.append(M._run(a, b, case.kind, *MC.geometry(case), case.crop, case.y))
+        out += [M.metric_planes(t, case.kind, case.crop, case.y) for t in (a, b)]
+    torch.cuda.synchronize()
+    return out

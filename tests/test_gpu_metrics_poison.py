@@ -1,0 +1,24 @@
+"""The metric kernels under LDS poison (the audit of test_gpu_lds_poison.py, for ssg_metrics.hip): metric_tiles stages
+both images' haloed planes and the row pass's five moments in LDS, and it and metric_fold keep three fixed-order block
+sums each there.  The profiling build fills the LDS of every CU with a word in front of every launch; every output must
+equal the product build's bit for bit (the same sources and flags, fixed-order sums; the profiling switches touch the
+host side of a launch only)."""
+import pytest
+import torch
+
+from test_gpu_lds_poison import PATTERNS, poisoned
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("word", PATTERNS)
+def test_metric_kernels_under_lds_poison(word):
+    if not torch.cuda.is_available():
+        pytest.skip("no GPU")
+    import test_gpu_metrics as tm
+    want = tm.poison_cases()
+    with poisoned(word):
+        got = tm.poison_cases()
+    assert len(got) == len(want) == 15
+    for i, (a, b) in enumerate(zip(got, want)):
+        assert bool(torch.isfinite(b.float()).all()), i
+        assert torch.equal(a, b), (i, float((a.float() - b.float()).abs().max()))

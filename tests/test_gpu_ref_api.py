@@ -416,6 +416,79 @@ def test_criterion_modules_on_materialised_tensors_match_torch(dev):
     assert float(L1Loss(1.0)(A.double(), Bt.double())) > 0 and float(L1Loss(1.0)(A.cpu(), Bt.cpu())) > 0
 
 
+# ---- the criteria kernels past one trip of their capped grids (ssg_grow.hip: 2,048 workgroups of 256 lanes for the sums,
+# 4 x 2,048 for the gradient, four elements per lane and trip on the 16-byte aligned path, one on the other) ----
+CRITERIA_SUMS_TRIP_N = 4 * 2048 * 256 + 4003          # 2,101,155: a second trip for 1,000 float4 lanes, a tail of 3
+CRITERIA_GRAD_TRIP_N = 4 * 4 * 2048 * 256 + 4099      # 8,392,707: the same for the gradient's grid (1,024 lanes, tail 3)
+CRITERIA_FLUSH_N = 33 * 4 * 2048 * 256 + 3            # 69,206,019: every lane adds its fp32 run of 32 float4 (aligned) or
+                                                      # 128 elements (not aligned: 132 trips) to fp64 once and goes on
+
+
+def _criteria_against_fp64(dev, n, views, reductions, seed):
+    """The recipe of test_criterion_modules_on_materialised_tensors_match_torch on n elements generated on the device:
+    rand ** 6 with the zero blocks, the exact ties and the 3e-11 element; `views` are (offset, length) windows of the
+    same two buffers (offset 1: a 4-byte aligned view, the scalar path).  Sums to 2e-6 relative (+ 1e-12 for KL),
+    gradients to 2e-6 of their maximum, against the same torch expressions in fp64 on the device."""
+    import torch.nn.functional as F
+    from ssl_amd.losses import KLDistanceLoss, L1Loss
+    g = torch.Generator(device=dev).manual_seed(seed)
+    base_a = torch.rand(n + 4, generator=g, device=dev) ** 6
+    base_b = torch.rand(n + 4, generator=g, device=dev) ** 6
+    base_a[:50] = 0.0                      # below the KL clamp
+    base_b[25:75] = 0.0
+    base_a[100:120] = base_b[100:120]      # exact ties: sign(0) = 0
+    base_a[200] = 3e-11
+    for offset, length in views:
+        A, Bt = base_a[offset:offset + length], base_b[offset:offset + length]
+        assert (A.data_ptr() % 16 == 0) == (offset % 4 == 0)
+        a64 = A.double().requires_grad_(True)
+        b64 = Bt.double()
+        for red in reductions:
+            x = A.detach().clone().requires_grad_(True) if offset == 0 else A.detach().requires_grad_(True)
+            l1 = L1Loss(2.5, red)(x, Bt)
+            kl = KLDistanceLoss(0.75, red)(x, Bt)
+            assert graph_nodes(l1, "_CriterionSumBackward") and graph_nodes(kl, "_CriterionSumBackward")
+            (l1 + kl).backward()
+            r1 = 2.5 * F.l1_loss(a64, b64, reduction=red)
+            r2 = 0.75 * F.kl_div(torch.clamp(input=a64, min=1e-10).log(), torch.clamp(input=b64, min=1e-10), reduction=red)
+            a64.grad = None
+            (r1 + r2).backward()
+            e1 = abs(float(l1) - float(r1)) / abs(float(r1))
+            e2 = abs(float(kl) - float(r2)) / abs(float(r2))
+            ref = a64.grad
+            eg = float((x.grad.double() - ref).abs().max()) / float(ref.abs().max())
+            print(f"TRIP criteria n {length} offset {offset} {red}: L1 rel {e1:.2e} KL rel {e2:.2e} grad / max {eg:.2e}")
+            assert abs(float(l1) - float(r1)) <= 2e-6 * abs(float(r1)), (length, offset, red, float(l1), float(r1))
+            assert abs(float(kl) - float(r2)) <= 2e-6 * abs(float(r2)) + 1e-12, (length, offset, red, float(kl), float(r2))
+            assert eg <= 2e-6, (length, offset, red)
+            del x, l1, kl, r1, r2, ref
+        del A, Bt, a64, b64
+    del base_a, base_b
+    torch.cuda.empty_cache()
+
+
+def test_criterion_kernels_past_one_grid_trip(dev):
+    """criteria_sums_kernel's second trip on both paths with criteria_finish_kernel folding all 2,048 slots, and
+    criteria_grad_kernel's second trip on its aligned path (the unaligned one is past its grid at either size)."""
+    _criteria_against_fp64(dev, CRITERIA_SUMS_TRIP_N, ((0, CRITERIA_SUMS_TRIP_N), (1, CRITERIA_SUMS_TRIP_N)),
+                           ("mean", "sum"), 21)
+    _criteria_against_fp64(dev, CRITERIA_GRAD_TRIP_N, ((0, CRITERIA_GRAD_TRIP_N),), ("mean", "sum"), 22)
+
+
+@pytest.mark.parametrize("offset", [0, 1], ids=["aligned", "offset1"])
+def test_criterion_sums_flush_their_fp32_runs(dev, offset):
+    """The smallest size at which every lane of criteria_sums_kernel adds a full fp32 run to its fp64 sum and goes on:
+    33 trips of float4 on the aligned buffers (block 0 takes the 3-element tail), 132 single-element trips through the
+    offset-1 view of the same buffers.  277 MB per tensor, the fp64 expressions stay on the device; a C5 eager SSG
+    tensor (629 M elements per image) takes this branch on every call.  (tools/criteria_flush_emulation.py: a correct
+    kernel is 4e-9 (L1) and 2e-8 (KL) from the fp64 sums here, so the 2e-6 of the smaller sizes holds unchanged.)"""
+    import time
+    t0 = time.perf_counter()
+    _criteria_against_fp64(dev, CRITERIA_FLUSH_N, ((offset, CRITERIA_FLUSH_N - offset),), ("sum",), 23)
+    torch.cuda.synchronize()
+    print(f"TRIP criteria flush offset {offset}: wall {time.perf_counter() - t0:.2f} s")
+
+
 def test_deferred_and_eager_loops_agree_on_random_batches(dev):
     """Property test of row R1: random batch sizes, image sizes that are not multiples of the tile sizes, mask
     densities (with empty images), mask dtypes and channel counts, kernel sizes with and without shared-term kernels,
