@@ -1735,8 +1735,9 @@ def test_f13_filter2d_vs_oracle_and_reference(dev, golden):
 def test_f14_diffjpeg_vs_oracle_and_reference(dev, golden):
     """ssg_diffjpeg / datapath.DiffJPEG against the fp64 oracle and the reference's own fp32 output
     (fixture F14: no rounding tie in it, so 3e-6 everywhere), tensor and scalar quality, output aliasing the input;
-    then a 3 x 3 x 100 x 135 random batch where the macroblocks holding a quotient within 2e-4 of k + 1/2 (torch.round
-    not decided at fp32) are left out -- they must be few -- and the rest agrees to 3e-6."""
+    then a 3 x 3 x 100 x 135 random batch where EVERY macroblock agrees to 3e-6 under some assignment of the roundings
+    that fp32 does not decide (tests/jpeg_reference.jpeg_match; none is left out)."""
+    from jpeg_reference import jpeg_match, report_line
     from oracle import datapath_oracle as dp
     from ssl_amd import _lib, datapath, engine
     g = golden("f14_diffjpeg")
@@ -1754,15 +1755,10 @@ def test_f14_diffjpeg_vs_oracle_and_reference(dev, golden):
     rng = np.random.default_rng(14)
     big = (np.round(rng.random((3, 3, 100, 135)) ** 2 * 255) / 255).astype(np.float32)
     qual = np.array([15.0, 60.0, 88.0], np.float32)
-    ref, quots = dp.diffjpeg(big, qual, return_quotients=True)
     yb = jp(T(big, dev), T(qual, dev)).cpu().numpy()
-    tie = np.zeros((3, 112 // 16, 144 // 16), bool)
-    for k, qq in enumerate(quots):
-        near = np.abs(qq - np.floor(qq) - 0.5) < 2e-4
-        s = 16 if k == 0 else 8
-        tie |= near.reshape(3, near.shape[1] // s, s, near.shape[2] // s, s).any((2, 4))
-    keep = ~np.repeat(np.repeat(tie, 16, 1), 16, 2)[:, None, :100, :135]
-    assert tie.mean() < 0.25 and np.abs((yb - ref) * keep).max() <= 3e-6
+    r = jpeg_match(yb, big, qual)
+    print(report_line("jpeg", "f14 random^2 3x3x100x135", r))
+    assert r["ok"] and r["worst"] <= 3e-6 and r["macroblocks"] == 3 * 7 * 9, r["failed"]
     with pytest.raises(NotImplementedError):
         datapath.DiffJPEG(differentiable=True)
     assert _lib.lib().ssg_diffjpeg(engine._ptr(x), engine._ptr(x2), 3, 40, 52, None, 0.0, engine._stream()) == -1
@@ -1772,7 +1768,9 @@ def test_f14_diffjpeg_vs_oracle_and_reference(dev, golden):
 def test_datapath_kernels_at_their_size_limits(dev):
     """USM / filter2D / JPEG at the smallest legal sizes and on exact tile multiples, against the fp64 oracle: reflect
     halos as wide as the image allows, single-plane batches, images smaller than one JPEG macroblock, a quality
-    tensor straddling 50 (the two branches of quality_to_factor)."""
+    tensor straddling 50 (the two branches of quality_to_factor).  JPEG through tests/jpeg_reference.jpeg_match: every
+    macroblock is compared."""
+    from jpeg_reference import jpeg_match, report_line
     from oracle import datapath_oracle as dp
     from ssl_amd import datapath
     rng = np.random.default_rng(41)
@@ -1795,16 +1793,10 @@ def test_datapath_kernels_at_their_size_limits(dev):
     for shape, qual in (((3, 3, 7, 5), [10.0, 50.0, 99.0]), ((2, 3, 32, 48), [49.0, 51.0])):
         x = q8(*shape)
         qv = np.asarray(qual, np.float32)
-        ref, quots = dp.diffjpeg(x, qv, return_quotients=True)
         y = datapath.DiffJPEG()(T(x, dev), T(qv, dev)).cpu().numpy()
-        Hp, Wp = quots[0].shape[1:]
-        tie = np.zeros((shape[0], Hp // 16, Wp // 16), bool)
-        for kq, qq in enumerate(quots):
-            s = 16 if kq == 0 else 8
-            near = np.abs(qq - np.floor(qq) - 0.5) < 2e-4
-            tie |= near.reshape(shape[0], Hp // 16, s, Wp // 16, s).any((2, 4))
-        keep = ~np.repeat(np.repeat(tie, 16, 1), 16, 2)[:, None, :shape[2], :shape[3]]
-        assert np.abs((y - ref) * keep).max() <= 3e-6 and tie.mean() < 0.3, shape
+        r = jpeg_match(y, x, qv)
+        print(report_line("jpeg", f"size limits {shape}", r))
+        assert r["ok"] and r["worst"] <= 3e-6, (shape, r["failed"])
 
 
 @pytest.mark.gpu
