@@ -633,6 +633,49 @@ int ssg_psnr_ssim(const void *a, const void *b, int kind, int B, int C, int H, i
 int ssg_metric_planes(const void *img, int kind, int B, int C, int H, int W, int crop_border, int y_channel,
                       float *planes_out, ssg_stream_t stream);
 
+/* ---------------------------------------------------------------- (K) ----
+ * NIQE (basicsr/metrics/niqe.py: calculate_niqe, niqe, compute_feature, estimate_aggd_param; to_y_channel and the 1/2
+ * imresize of basicsr/utils/matlab_functions.py in between), ssl_amd/csrc/ssg_niqe.hip.  One image in, one score per
+ * image out; nothing is copied to the host.  Computed in fp64 from the integer plane on (the reference keeps fp32 by
+ * accident of an astype; MATLAB's original is double): the contract, stage by stage, heads ssg_niqe.hip.
+ *   kind      the three SSG_METRIC_* kinds of section (J), read the same way, and
+ *             SSG_NIQE_F32_PLANE  fp32 (B,H,W) (C = 1): input_order 'HW', the given plane; `convert` is not looked at
+ *   convert   0 'y': to_y_channel as in section (J) (C = 1: the grey round trip); 1 'gray' (C = 3 only): OpenCV's
+ *             DOCUMENTED BGR2GRAY, 0.114 B + 0.587 G + 0.299 R on q / 255 in fp32, then * 255 -- OpenCV was never run
+ *             against it, its documentation alone pins the formula
+ *   plane 1   the converted plane, crop_border pixels off every side, rounded half to even, then its top-left
+ *             96 nbh x 96 nbw, nbh = (H - 2 crop) / 96, nbw = (W - 2 crop) / 96; plane 2 (48 nbh x 48 nbw) is its
+ *             antialiased bicubic half (not rounded).  Blocks are 96 x 96 and 48 x 48, nblk = nbh nbw per image.
+ *   features  (B, nblk, 36) fp64: 18 per scale, the reference's order; rows in its block order (block column outer).
+ *             A block side without a negative or without a positive value gives NaN entries (and alpha = 0.2, np.argmin's
+ *             answer to NaN), as in the reference.
+ *   score     sqrt(d' S^-1 d), S = (cov_pris + cov) / 2, by Cholesky (= the reference's pinv wherever S is finite);
+ *             NaN for fewer than two NaN-free rows.  mu_pris (36), cov_pris (36,36) fp64 on the device.
+ * A NaN in a float input is unspecified.
+ * Status, decided before any launch with the outputs untouched: SSG_E_BADARG for a null pointer, B, H or W <= 0, C not
+ * 1 or 3 (the plane kind: not 1), crop_border < 0, an unknown kind, convert not 0 or 1, or 'gray' with C = 1;
+ * SSG_E_TOOLARGE for B > 65535 or 2^31 elements and more; SSG_E_IMAGESMALL for a cropped side shorter than 96 (no
+ * block); SSG_E_WORKSPACE for workspace_bytes < ssg_niqe_workspace_bytes(...) (0 for a shape outside the domain; it
+ * holds both planes, the features and one flag per row: about 6.2 bytes per pixel of plane 1); SSG_E_ALIGN for a
+ * workspace that is not 16-byte aligned.
+ * No atomics, fixed summation orders (bit-reproducible), no synchronisation or host read.  The first call per device
+ * of ssg_niqe / ssg_niqe_features uploads the 306 KiB table of the alpha search (one allocation, one blocking copy):
+ * make it outside stream capture.
+ * ssg_niqe: out (B) fp64 on the device.  Five launches.
+ * ssg_niqe_planes: plane1 (B,96 nbh,96 nbw) fp32, plane2 (B,48 nbh,48 nbw) fp64.  Two launches.
+ * ssg_niqe_features: feat (B,nblk,36) fp64; the planes go to the workspace.  Three launches.
+ * ssg_niqe_table: HOST function, no device: table_out (4,9801) fp64 = gam, r(gam) = G(2/g)^2 / (G(1/g) G(3/g)),
+ *   G(1/g) / G(3/g), G(2/g) / G(1/g) -- what the device's table holds. */
+#define SSG_NIQE_F32_PLANE 3
+size_t ssg_niqe_workspace_bytes(int B, int C, int H, int W, int crop_border);
+int ssg_niqe(const void *img, int kind, int B, int C, int H, int W, int crop_border, int convert, const double *mu_pris,
+             const double *cov_pris, double *out, void *workspace, size_t workspace_bytes, ssg_stream_t stream);
+int ssg_niqe_planes(const void *img, int kind, int B, int C, int H, int W, int crop_border, int convert, float *plane1,
+                    double *plane2, ssg_stream_t stream);
+int ssg_niqe_features(const void *img, int kind, int B, int C, int H, int W, int crop_border, int convert, double *feat,
+                      void *workspace, size_t workspace_bytes, ssg_stream_t stream);
+int ssg_niqe_table(double *table_out);
+
 #ifdef SSG_PROFILE
 /* PROFILING BUILD ONLY (libssg_hip_prof.so, compiled with -DSSG_PROFILE; the product library libssg_hip.so does not
  * export this symbol and has no code path that skips work).  Results are WRONG while a mask is set: skip kernel

@@ -80,6 +80,11 @@ PROTOTYPES = {
     "ssg_metric_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
     "ssg_psnr_ssim": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _sz, _vp]),
     "ssg_metric_planes": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
+    "ssg_niqe_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
+    "ssg_niqe": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "ssg_niqe_planes": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "ssg_niqe_features": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _sz, _vp]),
+    "ssg_niqe_table": (_i, [_vp]),
     # include/similarity.h: the reference operator's own (void, stream-less) interface
     "ssg_ref_compute_similarity": (None, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i]),
     "ssg_ref_compute_similarity_backward": (None, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i]),

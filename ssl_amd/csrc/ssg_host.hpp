@@ -108,6 +108,8 @@ int launch_synth_kernels(const ssg_kernel_record *records_dev, int n, int pad_to
 // ---- ssg_metrics.hip: PSNR / SSIM (its entry points are defined beside its kernels) ----
 size_t metric_workspace_bytes(int B, int C, int H, int W, int crop);
 
+// ---- ssg_niqe.hip: NIQE (entry points beside its kernels; nothing of it is called from another file) ----
+
 // ---- ssg_api.hip ----
 // host-mapped {rows for the direct kernels, dense tiles} of the device's last plan, written by the edge-list builder's
 // scan kernel (nullptr: no hint wanted, or none allocated yet and `st` is being captured)

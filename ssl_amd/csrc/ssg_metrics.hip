@@ -45,6 +45,7 @@ namespace metric {
 
 using pixel::NT;
 using pixel::check_workspace;
+using pixel::plane_value;
 
 constexpr int TW = 32, TH = 16;          // map tile
 constexpr int R = 5, K = 2 * R + 1;      // the 11-tap window
@@ -66,30 +67,6 @@ struct Args {
   int ntx, nty, tiles;  // tiles per row, per column, per image (P nty ntx)
   int wg;               // workgroups per image
 };
-
-// plane p of image n at (y, x) of the UNCROPPED image, after quantise and Y
-__device__ __forceinline__ float plane_value(const void *img, const Args &a, int n, int p, int y, int x) {
-  const size_t hw = (size_t)a.H * a.W;
-  const size_t at = (size_t)y * a.W + x;
-  float q[3];
-  const int nq = a.ych ? a.C : 1;       // Y reads every channel, a plain plane its own
-  for (int i = 0; i < nq; ++i) {
-    const int c = a.ych ? i : p;        // BGR index
-    if (a.kind == SSG_METRIC_F32_RGB) {
-      const float v = ((const float *)img)[((size_t)n * a.C + (a.C - 1 - c)) * hw + at];
-      q[i] = rintf(fminf(fmaxf(v, 0.f), 1.f) * 255.0f);
-    } else if (a.kind == SSG_METRIC_U8_HWC) {
-      q[i] = (float)((const uint8_t *)img)[((size_t)n * hw + at) * a.C + c];
-    } else {
-      q[i] = (float)((const uint8_t *)img)[((size_t)n * a.C + c) * hw + at];
-    }
-  }
-  if (!a.ych) return q[0];
-  if (a.C == 1) return (q[0] / 255.0f) * 255.0f;
-  const double vb = (double)(q[0] / 255.0f), vg = (double)(q[1] / 255.0f), vr = (double)(q[2] / 255.0f);
-  const double t = ((24.966 * vb + 128.553 * vg) + 65.481 * vr) + 16.0;
-  return (float)(t / 255.0) * 255.0f;
-}
 
 __global__ __launch_bounds__(NT) void metric_planes(Args a) {
   const size_t n = (size_t)a.B * a.P * a.Hc * a.Wc;

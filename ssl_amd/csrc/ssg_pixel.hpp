@@ -1,6 +1,7 @@
 // What the pixel-loss kernels share (ssg_ldl.hip, ssg_bbl.hip, ssg_bp.hip): the workgroup size, sgn, the fixed-order fp64
 // workgroup sum, the reflect-padded 32 x 16 tile of the two local-variance kernels (ldl_map, flat_mask) and the
-// workspace test that ends their entry points' argument checks.  One definition each: a fix reaches all three files.
+// workspace test that ends their entry points' argument checks, and the metric files' (ssg_metrics.hip, ssg_niqe.hip)
+// quantised / Y plane value.  One definition each: a fix reaches every file.
 #pragma once
 #include "../../include/ssg_hip.h"
 
@@ -46,6 +47,32 @@ __device__ __forceinline__ void load_halo_tile(float (&tile)[LH][LW], int ty0, i
     const int ly = i / lw, lx = i - ly * lw;
     tile[ly][lx] = value(reflect_clamp(ty0 - R + ly, H) * W + reflect_clamp(tx0 - R + lx, W));
   }
+}
+
+// ---- the metrics' planes (ssg_metrics.hip, ssg_niqe.hip) ----
+// plane p of image n at (y, x) of the UNCROPPED image, after quantise and Y; Args holds kind, C, H, W and ych
+template <class Args>
+__device__ __forceinline__ float plane_value(const void *img, const Args &a, int n, int p, int y, int x) {
+  const size_t hw = (size_t)a.H * a.W;
+  const size_t at = (size_t)y * a.W + x;
+  float q[3];
+  const int nq = a.ych ? a.C : 1;       // Y reads every channel, a plain plane its own
+  for (int i = 0; i < nq; ++i) {
+    const int c = a.ych ? i : p;        // BGR index
+    if (a.kind == SSG_METRIC_F32_RGB) {
+      const float v = ((const float *)img)[((size_t)n * a.C + (a.C - 1 - c)) * hw + at];
+      q[i] = rintf(fminf(fmaxf(v, 0.f), 1.f) * 255.0f);
+    } else if (a.kind == SSG_METRIC_U8_HWC) {
+      q[i] = (float)((const uint8_t *)img)[((size_t)n * hw + at) * a.C + c];
+    } else {
+      q[i] = (float)((const uint8_t *)img)[((size_t)n * a.C + c) * hw + at];
+    }
+  }
+  if (!a.ych) return q[0];
+  if (a.C == 1) return (q[0] / 255.0f) * 255.0f;
+  const double vb = (double)(q[0] / 255.0f), vg = (double)(q[1] / 255.0f), vr = (double)(q[2] / 255.0f);
+  const double t = ((24.966 * vb + 128.553 * vg) + 65.481 * vr) + 16.0;
+  return (float)(t / 255.0) * 255.0f;
 }
 
 // ---- host ----

@@ -1,4 +1,4 @@
-"""PSNR and SSIM as the reference's validation loop computes them, on the GPU (ssl_amd/csrc/ssg_metrics.hip).
+"""PSNR, SSIM and NIQE as the reference computes them, on the GPU (ssl_amd/csrc/ssg_metrics.hip, ssg_niqe.hip).
 
 Named as `basicsr.metrics` names them: `calculate_psnr`, `calculate_ssim` and `calculate_metric` keep the reference's
 signatures, its ValueError and its shape assertion; `psnr_ssim` is the batched call on a model's own tensors (what
@@ -7,7 +7,15 @@ signatures, its ValueError and its shape assertion; `psnr_ssim` is the batched c
 
 Contract: include/ssg_hip.h section (J).  A NaN in a float input is unspecified, as in the reference.  An image whose
 cropped side is shorter than 11 is refused (the reference's SSIM would be the mean of an empty map); there is no CPU
-path."""
+path.
+
+NIQE (section (K)): `calculate_niqe` keeps the reference's signature, `niqe` is the batched call on a model's tensors,
+`MetricAverager.add_niqe` its running mean.  It is computed in fp64 from the rounded plane on.  The pristine model
+(mu_pris_param, cov_pris_param) is the reference's data and does not ship with the package: `load_niqe_params` takes
+it from a path, a mapping, the environment variable SSL_AMD_NIQE_PARAMS or an installed basicsr.  `calculate_metric`
+and `add_all` do not dispatch to NIQE (no reference YAML lists it under val.metrics)."""
+import importlib.util
+import os
 from copy import deepcopy
 
 import numpy as np
@@ -16,9 +24,15 @@ import torch
 from . import _lib
 from .engine import _launch, _need_gpu, _ptr, _workspace
 
-__all__ = ["calculate_psnr", "calculate_ssim", "calculate_metric", "psnr_ssim", "MetricAverager"]
+__all__ = ["calculate_psnr", "calculate_ssim", "calculate_niqe", "calculate_metric", "psnr_ssim", "niqe",
+           "load_niqe_params", "MetricAverager"]
 
 KIND_F32_RGB, KIND_U8_HWC, KIND_U8_CHW = 0, 1, 2
+KIND_F32_PLANE = 3                      # NIQE only: a float32 (B,H,W) plane (input_order 'HW')
+NIQE_BLOCK, NIQE_FEATURES = 96, 36
+NIQE_PARAMS_ENV = "SSL_AMD_NIQE_PARAMS"
+NIQE_PARAMS_FILE = "niqe_pris_params.npz"
+_CONVERT = {'y': 0, 'gray': 1}
 
 
 def _device():
@@ -111,6 +125,148 @@ def calculate_ssim(img, img2, crop_border, input_order='HWC', test_y_channel=Fal
     return float(_both(img, img2, crop_border, input_order, test_y_channel)[0, 1])
 
 
+# ---------------------------------------------------------------------------------------------------------- NIQE ---
+_niqe_params = {}                       # (source, device) -> (mu, cov)
+
+
+def _find_niqe_params():
+    """The parameter file's path when no source is given: the environment variable, then an installed basicsr."""
+    path = os.environ.get(NIQE_PARAMS_ENV)
+    if path:
+        return path
+    try:
+        spec = importlib.util.find_spec("basicsr")          # located, never imported
+    except (ImportError, ValueError):
+        spec = None
+    for root in (spec.submodule_search_locations or []) if spec is not None else []:
+        cand = os.path.join(root, "metrics", NIQE_PARAMS_FILE)
+        if os.path.exists(cand):
+            return cand
+    raise FileNotFoundError(
+        f"ssl_amd: NIQE needs the pristine model ({NIQE_PARAMS_FILE}: mu_pris_param, cov_pris_param), which is the "
+        f"reference's data and does not ship with this package: set {NIQE_PARAMS_ENV} to its path, install basicsr "
+        f"(the file lies beside basicsr.metrics), or pass niqe_pris_params= (a path or a mapping of the two arrays)")
+
+
+def load_niqe_params(source=None, device=None):
+    """(mu (36,), cov (36,36)) as float64 tensors on `device` (the current GPU by default), cached per source and
+    device.  `source`: a path to niqe_pris_params.npz, a mapping holding mu_pris_param and cov_pris_param, or None
+    (SSL_AMD_NIQE_PARAMS, then the file beside an installed basicsr.metrics, else FileNotFoundError)."""
+    dev = torch.device(device) if device is not None else _device()
+    mapping = source is not None and not isinstance(source, (str, os.PathLike))
+    if not mapping:
+        path = os.fspath(source) if source is not None else _find_niqe_params()
+        key = (os.path.abspath(path), str(dev))
+        if key in _niqe_params:
+            return _niqe_params[key]
+        source = np.load(path)
+    mu = np.asarray(source["mu_pris_param"], dtype=np.float64).reshape(-1)
+    cov = np.asarray(source["cov_pris_param"], dtype=np.float64)
+    if mu.shape != (NIQE_FEATURES,) or cov.shape != (NIQE_FEATURES, NIQE_FEATURES):
+        raise ValueError(f"ssl_amd: NIQE parameters are (36,) and (36,36), got {mu.shape} and {cov.shape}")
+    out = (torch.from_numpy(mu).to(dev), torch.from_numpy(np.ascontiguousarray(cov)).to(dev))
+    if not mapping:
+        _niqe_params[key] = out
+    return out
+
+
+def _niqe_geometry(t, kind):
+    if kind == KIND_U8_HWC:
+        B, H, W, C = t.shape
+    elif kind == KIND_F32_PLANE:
+        (B, H, W), C = t.shape, 1
+    else:
+        B, C, H, W = t.shape
+    return B, C, H, W
+
+
+def _niqe_blocks(H, W, crop_border):
+    return max(H - 2 * crop_border, 0) // NIQE_BLOCK, max(W - 2 * crop_border, 0) // NIQE_BLOCK
+
+
+def _niqe_run(t, kind, crop_border, convert_to, params):
+    """(B,) float64 scores on the device for a contiguous device tensor laid out as `kind` says."""
+    _need_gpu(t)
+    B, C, H, W = _niqe_geometry(t, kind)
+    mu, cov = load_niqe_params(params, t.device)
+    L = _lib.lib()
+    out = torch.empty((B,), dtype=torch.float64, device=t.device)
+    ws, nb = _workspace(L.ssg_niqe_workspace_bytes(B, C, H, W, int(crop_border)), t.device)
+    _launch(t.device, L.ssg_niqe, _ptr(t), kind, B, C, H, W, int(crop_border), _CONVERT[convert_to], _ptr(mu), _ptr(cov),
+            _ptr(out), _ptr(ws), nb)
+    return out
+
+
+def niqe_planes(t, kind, crop_border=0, convert_to='y'):
+    """The two planes NIQE is computed on: (B,96 nbh,96 nbw) float32 (the rounded plane) and (B,48 nbh,48 nbw) float64
+    (its antialiased bicubic half), for a contiguous device tensor laid out as `kind` says."""
+    _need_gpu(t)
+    B, C, H, W = _niqe_geometry(t, kind)
+    nbh, nbw = _niqe_blocks(H, W, crop_border)
+    p1 = torch.empty((B, 96 * nbh, 96 * nbw), dtype=torch.float32, device=t.device)
+    p2 = torch.empty((B, 48 * nbh, 48 * nbw), dtype=torch.float64, device=t.device)
+    _launch(t.device, _lib.lib().ssg_niqe_planes, _ptr(t), kind, B, C, H, W, int(crop_border), _CONVERT[convert_to],
+            _ptr(p1), _ptr(p2))
+    return p1, p2
+
+
+def niqe_features(t, kind, crop_border=0, convert_to='y'):
+    """The (B,nblk,36) float64 feature rows, blocks in the reference's order (block column outer)."""
+    _need_gpu(t)
+    B, C, H, W = _niqe_geometry(t, kind)
+    nbh, nbw = _niqe_blocks(H, W, crop_border)
+    L = _lib.lib()
+    feat = torch.empty((B, nbh * nbw, NIQE_FEATURES), dtype=torch.float64, device=t.device)
+    ws, nb = _workspace(L.ssg_niqe_workspace_bytes(B, C, H, W, int(crop_border)), t.device)
+    _launch(t.device, L.ssg_niqe_features, _ptr(t), kind, B, C, H, W, int(crop_border), _CONVERT[convert_to], _ptr(feat),
+            _ptr(ws), nb)
+    return feat
+
+
+def _as_niqe_image(img, input_order):
+    """The device tensor and kind of an image as calculate_niqe receives it: 'HW' keeps its float values (the kernel
+    rounds them half to even, as the reference's img.round() does); 'HWC' / 'CHW' are images holding 0 .. 255."""
+    if input_order != 'HW':
+        return _as_image(img, input_order)
+    t = torch.from_numpy(np.ascontiguousarray(img)) if isinstance(img, np.ndarray) else img
+    if t.dim() != 2:
+        raise ValueError(f"ssl_amd: input_order 'HW' takes an (H,W) plane, got {tuple(t.shape)}")
+    if not t.is_cuda:
+        t = t.to(_device())
+    return t.to(torch.float32).contiguous()[None], KIND_F32_PLANE
+
+
+def calculate_niqe(img, crop_border, input_order='HWC', convert_to='y', **kwargs):
+    """basicsr.metrics.calculate_niqe: an image with range [0, 255], BGR for 'HWC' / 'CHW', or an (H,W) plane for 'HW';
+    a numpy array (uploaded) or a tensor.  `niqe_pris_params=` names the pristine model (see load_niqe_params).
+    Returns a Python float; NaN where fewer than two blocks give NaN-free features (the reference's pinv raises or
+    returns NaN there)."""
+    if input_order not in ['HWC', 'CHW', 'HW']:
+        raise ValueError(f'Wrong input_order {input_order}. Supported input_orders are "HWC", "CHW" and "HW"')
+    if convert_to not in _CONVERT:
+        raise ValueError(f'Wrong convert_to {convert_to}. Supported values are "y" and "gray"')
+    t, kind = _as_niqe_image(img, input_order)
+    return float(_niqe_run(t, kind, crop_border, convert_to, kwargs.get('niqe_pris_params'))[0])
+
+
+def niqe(sr, crop_border=0, convert_to='y', niqe_pris_params=None):
+    """NIQE of float (N,3,H,W) (or (3,H,W)) RGB tensors in nominal [0, 1], as `visuals['result']` holds them: what the
+    reference gets from tensor2img followed by calculate_niqe.  Returns a device (N,) float64 tensor; runs on the
+    current stream without synchronising with the host (once the parameters and the alpha table are on the device:
+    the first call per device uploads them)."""
+    if not (torch.is_tensor(sr) and sr.is_floating_point()):
+        raise TypeError("ssl_amd: niqe takes floating-point tensors (use calculate_niqe for images)")
+    if convert_to not in _CONVERT:
+        raise ValueError(f'Wrong convert_to {convert_to}. Supported values are "y" and "gray"')
+    if sr.dim() == 3:
+        sr = sr[None]
+    if sr.dim() != 4:
+        raise ValueError(f"ssl_amd: niqe takes (N,C,H,W) or (C,H,W) tensors, got {tuple(sr.shape)}")
+    dev = sr.device if sr.is_cuda else _device()
+    a = sr.detach().to(device=dev, dtype=torch.float32).contiguous()
+    return _niqe_run(a, KIND_F32_RGB, crop_border, convert_to, niqe_pris_params)
+
+
 _COLUMN = {"calculate_psnr": 0, "calculate_ssim": 1}
 
 
@@ -176,6 +332,12 @@ class MetricAverager:
             if key not in done:
                 done[key] = psnr_ssim(sr, gt, *key)
             self._accumulate(name, done[key][:, col])
+
+    def add_niqe(self, name, sr, **opt):
+        """One NIQE value per image of `sr` (float RGB tensors in [0, 1]); opt: crop_border, convert_to,
+        niqe_pris_params."""
+        out = niqe(sr, opt.get('crop_border', 0), opt.get('convert_to', 'y'), opt.get('niqe_pris_params'))
+        self._accumulate(name, out)
 
     def result(self):
         if not self._sum:
