@@ -676,6 +676,49 @@ int ssg_niqe_features(const void *img, int kind, int B, int C, int H, int W, int
                       void *workspace, size_t workspace_bytes, ssg_stream_t stream);
 int ssg_niqe_table(double *table_out);
 
+/* ---------------------------------------------------------------- (L) ----
+ * StableSR's colour correction of the Diffusion fork's samples (scripts/wavelet_color_fix.py: wavelet_blur,
+ * wavelet_decomposition, wavelet_reconstruction, calc_mean_std, adaptive_instance_normalization, and the
+ * clamp((x + 1) / 2, 0, 1) and 255 x -> byte its callers append), ssl_amd/csrc/ssg_colorfix.hip.  Every tensor fp32
+ * contiguous (B,C,H,W), any B, C, H, W >= 1, planes independent; content first, style second, as in the reference.
+ *   blur      [1/4, 1/2, 1/4] per axis at -radius, 0, +radius, the tap coordinate clamped to the plane (replicate
+ *             padding by `radius`, then the dilated 3 x 3 convolution); rows first, then columns.
+ *   levels    1 .. 5 (5: the reference's default and only use): level i has radius 2^(i-1); low = the image after all
+ *             levels, high = image - low (the reference sums the per-level differences, which telescope to this).
+ *   wavelet   out = content + low(style - content), which is high(content) + low(style) in real arithmetic: the blur
+ *             is linear and clamps both images alike.  Within 64 * 2^-24 * max(|content|, |style|) of the fp64 value.
+ *   stats     per plane {mean, sqrt(var + eps)}, var unbiased (n - 1; a plane of one element gives NaN, as torch), fp64
+ *             sums in a fixed order over a fixed chunking: the same bits whatever the batch around the plane.
+ *             stats (n_img, B C, 2) fp64 on the device, image 0 = content, image 1 = style (n_img = 1 for a null style).
+ *   adain     out = (x - mean_c) / std_c * std_s + mean_s on the statistics rounded to fp32; stats (2, B C, 2) as
+ *             ssg_colorfix_stats wrote it, or NULL: the epilogue alone ('nofix').
+ *   out_kind  SSG_COLORFIX_RAW v, fp32 (B,C,H,W); SSG_COLORFIX_UNIT u = clamp((v + 1) / 2, 0, 1), fp32 (B,C,H,W), a NaN
+ *             stays a NaN; SSG_COLORFIX_U8_NHWC (uint8)(255.0f u) truncated, uint8 (B,H,W,C), a NaN gives 0.
+ * Status, decided before any launch with the outputs untouched: SSG_E_BADARG for a null pointer (those marked nullable
+ * excepted: `style` of ssg_colorfix_stats, `stats` of ssg_colorfix_adain, one of high / low), an output that is an input
+ * (ssg_colorfix_adain may run in place for the two fp32 kinds), B, C, H or W <= 0, radius < 1, levels < 1, an unknown
+ * out_kind, eps < 0 or NaN; SSG_E_TOOLARGE for levels > 5 or 2^31 elements and more; SSG_E_WORKSPACE for
+ * workspace_bytes < ssg_colorfix_workspace_bytes(...) (0 for a shape outside the domain; 48 bytes per 4,096 elements of a
+ * plane: the chunk sums of both images); SSG_E_ALIGN for a workspace that is not 16-byte aligned.
+ * No atomics, no synchronisation, no allocation, no host read; bit-reproducible.
+ * ssg_wavelet_blur: one launch, taps read from global memory, any radius >= 1.
+ * ssg_wavelet_decompose: high, low (B,C,H,W), either may be NULL.  One launch (64 x 64 tiles, 128,016 B of LDS).
+ * ssg_colorfix_wavelet: one launch of the same tile pass.
+ * ssg_colorfix_stats: two launches for one image or two.   ssg_colorfix_adain: one launch. */
+#define SSG_COLORFIX_RAW 0
+#define SSG_COLORFIX_UNIT 1
+#define SSG_COLORFIX_U8_NHWC 2
+int ssg_wavelet_blur(const float *image, int B, int C, int H, int W, int radius, float *out, ssg_stream_t stream);
+int ssg_wavelet_decompose(const float *image, int B, int C, int H, int W, int levels, float *high, float *low,
+                          ssg_stream_t stream);
+int ssg_colorfix_wavelet(const float *content, const float *style, int B, int C, int H, int W, int levels, int out_kind,
+                         void *out, ssg_stream_t stream);
+size_t ssg_colorfix_workspace_bytes(int B, int C, int H, int W);
+int ssg_colorfix_stats(const float *content, const float *style, int B, int C, int H, int W, double eps, double *stats,
+                       void *workspace, size_t workspace_bytes, ssg_stream_t stream);
+int ssg_colorfix_adain(const float *content, const double *stats, int B, int C, int H, int W, int out_kind, void *out,
+                       ssg_stream_t stream);
+
 #ifdef SSG_PROFILE
 /* PROFILING BUILD ONLY (libssg_hip_prof.so, compiled with -DSSG_PROFILE; the product library libssg_hip.so does not
  * export this symbol and has no code path that skips work).  Results are WRONG while a mask is set: skip kernel

@@ -85,6 +85,12 @@ PROTOTYPES = {
     "ssg_niqe_planes": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     "ssg_niqe_features": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _sz, _vp]),
     "ssg_niqe_table": (_i, [_vp]),
+    "ssg_wavelet_blur": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp]),
+    "ssg_wavelet_decompose": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
+    "ssg_colorfix_wavelet": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp]),
+    "ssg_colorfix_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "ssg_colorfix_stats": (_i, [_vp, _vp, _i, _i, _i, _i, ctypes.c_double, _vp, _vp, _sz, _vp]),
+    "ssg_colorfix_adain": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
     # include/similarity.h: the reference operator's own (void, stream-less) interface
     "ssg_ref_compute_similarity": (None, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i]),
     "ssg_ref_compute_similarity_backward": (None, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i]),

@@ -110,6 +110,9 @@ size_t metric_workspace_bytes(int B, int C, int H, int W, int crop);
 
 // ---- ssg_niqe.hip: NIQE (entry points beside its kernels; nothing of it is called from another file) ----
 
+// ---- ssg_colorfix.hip: wavelet / AdaIN colour correction (entry points beside its kernels; nothing of it is called
+// from another file) ----
+
 // ---- ssg_api.hip ----
 // host-mapped {rows for the direct kernels, dense tiles} of the device's last plan, written by the edge-list builder's
 // scan kernel (nullptr: no hint wanted, or none allocated yet and `st` is being captured)
