@@ -719,6 +719,41 @@ int ssg_colorfix_stats(const float *content, const float *style, int B, int C, i
 int ssg_colorfix_adain(const float *content, const double *stats, int B, int C, int H, int W, int out_kind, void *out,
                        ssg_stream_t stream);
 
+/* ---------------------------------------------------------------- (M) ----
+ * KAIR's SSIM criterion (GAN-Based-SR/train_BSGRAN/models/loss_ssim.py: _ssim, SSIMLoss, ssim -- the pytorch-ssim
+ * module, G_lossfn_type "ssim" of models/model_ssl.py), ssl_amd/csrc/ssg_ssim.hip.  x, y fp32 contiguous (B,C,H,W), any
+ * B, C, H, W >= 1 (sides shorter than the window included), planes independent; everything is computed in fp32 but
+ * the sums.  With `*` the per-plane 'same' convolution (zero padding) under the window w_ij = g_i g_j, g the
+ * window_size normalised Gaussian taps of sigma 1.5 in fp32:
+ *   mx = w*x, my = w*y, exx = w*x^2, eyy = w*y^2, exy = w*xy
+ *   A1 = 2 mx my + C1, A2 = 2 (exy - mx my) + C2, B1 = mx^2 + my^2 + C1, B2 = (exx - mx^2) + (eyy - my^2) + C2,
+ *   C1 = 0.01^2, C2 = 0.03^2, S = A1 A2 / (B1 B2)
+ *   sums_out[b] = the sum of S over image b, b < B; sums_out[B] = their sum in image order: B + 1 DOUBLES on the
+ *         device (the map values are fp32, their accumulation is fp64).  SSIM is sums_out[B] / (B C H W), or
+ *         sums_out[b] / (C H W) per image; sign and weight are the caller's.
+ *   grad_x (nullable) = d sums_out[B] / d x = w*P + 2 x (w*Q) + y (w*R), P = dS/dmx (through both variances), Q =
+ *         -S / B2, R = 2 A1 / (B1 B2), each zero outside the image; every element is written.  UNSCALED: multiply by
+ *         the upstream coefficient of S (1 / (B C H W) for the mean).  S is symmetric, so the gradient with respect to
+ *         y is the call with x and y exchanged.  With a null grad_x the tile pass skips the ring and the store.
+ * window_size is odd and <= 11; a smaller window is the 11-tap kernel with zero taps beyond its radius.
+ * Status, decided before any launch with the outputs untouched: SSG_E_BADARG for a null pointer (grad_x excepted), a
+ * grad_x that is x or y, B, C, H or W <= 0, or a window_size that is even, < 1 or > 11; SSG_E_TOOLARGE for B > 65535 or
+ * 2^31 elements and more; SSG_E_WORKSPACE for workspace_bytes < ssg_ssim_workspace_bytes(...) (0 for a shape outside
+ * the domain; one double per workgroup: min(C ceil(H / 32) ceil(W / 64), ssg_ssim_grid_cap()) per image, padded to
+ * 256 bytes); SSG_E_ALIGN for a workspace that is not 16-byte aligned.
+ * Two launches.  No atomics, fixed summation orders: bit-reproducible, and image b of a batch gets the bits it gets
+ * alone.  No allocation, synchronisation or host read.
+ * ssg_ssim_grid_cap: the most workgroups per image the tile pass launches (512); beyond it a workgroup walks several
+ *   tiles.
+ * ssg_ssim_taps: HOST function, no device: taps_out[11] = the fp32 taps the kernels use, centred, zeros around a
+ *   window shorter than 11 (the reference's gaussian(window_size, 1.5)). */
+size_t ssg_ssim_workspace_bytes(int B, int C, int H, int W);
+int ssg_ssim_grid_cap(void);
+int ssg_ssim_taps(int window_size, float *taps_out);
+int ssg_ssim_loss(const float *x, const float *y, int B, int C, int H, int W, int window_size,
+                  float *grad_x /* nullable */, double *sums_out, void *workspace, size_t workspace_bytes,
+                  ssg_stream_t stream);
+
 #ifdef SSG_PROFILE
 /* PROFILING BUILD ONLY (libssg_hip_prof.so, compiled with -DSSG_PROFILE; the product library libssg_hip.so does not
  * export this symbol and has no code path that skips work).  Results are WRONG while a mask is set: skip kernel

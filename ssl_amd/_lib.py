@@ -91,6 +91,10 @@ PROTOTYPES = {
     "ssg_colorfix_workspace_bytes": (_sz, [_i, _i, _i, _i]),
     "ssg_colorfix_stats": (_i, [_vp, _vp, _i, _i, _i, _i, ctypes.c_double, _vp, _vp, _sz, _vp]),
     "ssg_colorfix_adain": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
+    "ssg_ssim_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "ssg_ssim_grid_cap": (_i, []),
+    "ssg_ssim_taps": (_i, [_i, _vp]),
+    "ssg_ssim_loss": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
     # include/similarity.h: the reference operator's own (void, stream-less) interface
     "ssg_ref_compute_similarity": (None, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i]),
     "ssg_ref_compute_similarity_backward": (None, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i]),

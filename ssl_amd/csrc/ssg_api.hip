@@ -1293,6 +1293,18 @@ int ssg_criteria_grad(const float *pred, const float *target, size_t n, const fl
   return launch_criteria_grad(pred, target, n, coef, grad_pred, (hipStream_t)stream);
 }
 
+size_t ssg_ssim_workspace_bytes(int B, int C, int H, int W) { return ssim_workspace_bytes(B, C, H, W); }
+
+int ssg_ssim_grid_cap(void) { return ssim_grid_cap(); }
+
+int ssg_ssim_taps(int window_size, float *taps_out) { return ssim_taps(window_size, taps_out); }
+
+int ssg_ssim_loss(const float *x, const float *y, int B, int C, int H, int W, int window_size, float *grad_x,
+                  double *sums_out, void *workspace, size_t workspace_bytes, ssg_stream_t stream) {
+  return launch_ssim_loss(x, y, B, C, H, W, window_size, grad_x, sums_out, workspace, workspace_bytes,
+                          (hipStream_t)stream);
+}
+
 int ssg_device_status(ssg_stream_t stream) {
   int *w = device_status_word();
   if (!w) return 0;

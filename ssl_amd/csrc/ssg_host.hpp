@@ -113,6 +113,13 @@ size_t metric_workspace_bytes(int B, int C, int H, int W, int crop);
 // ---- ssg_colorfix.hip: wavelet / AdaIN colour correction (entry points beside its kernels; nothing of it is called
 // from another file) ----
 
+// ---- ssg_ssim.hip: KAIR's SSIM criterion, loss and gradient in two launches ----
+int ssim_grid_cap();
+int ssim_taps(int window_size, float *taps);                  // host only: the 11 centred fp32 taps
+size_t ssim_workspace_bytes(int B, int C, int H, int W);
+int launch_ssim_loss(const float *x, const float *y, int B, int C, int H, int W, int window_size, float *grad_x,
+                     double *sums_out, void *workspace, size_t workspace_bytes, hipStream_t st);
+
 // ---- ssg_api.hip ----
 // host-mapped {rows for the direct kernels, dense tiles} of the device's last plan, written by the edge-list builder's
 // scan kernel (nullptr: no hint wanted, or none allocated yet and `st` is being captured)

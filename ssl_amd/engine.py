@@ -769,3 +769,87 @@ def bp_loss(x, lq, s=4, loss_weight=1.0, reduction='mean'):
         return loss, grad
 
     return _FusedLossFn.apply(x, call)
+
+
+# --------------------------------------------------------------------- KAIR's SSIM criterion (ssg_ssim.hip) ----
+SSIM_MAX_WINDOW = 11
+
+
+def _ssim_sums(x, y, window_size, want_grad):
+    """One ssg_ssim_loss call: (sums (B + 1,) fp64 -- the map summed per image, then over the batch -- and
+    d sums[B] / d x or None)."""
+    B, C, H, W = x.shape
+    sums = torch.empty(B + 1, dtype=torch.float64, device=x.device)
+    grad = torch.empty_like(x) if want_grad else None
+    ws, nb = _workspace(_lib.lib().ssg_ssim_workspace_bytes(B, C, H, W), x.device)
+    _launch(x.device, _lib.lib().ssg_ssim_loss, _ptr(x), _ptr(y), B, C, H, W, window_size, _ptr(grad), _ptr(sums),
+            _ptr(ws), nb)
+    return sums, grad
+
+
+class _SSIMFn(torch.autograd.Function):
+    """SSIM of (img1, img2) with the UNSCALED gradients d (sum of the map) / d img formed in the forward call: one C call
+    per argument that requires grad (the second with the roles swapped -- the map is symmetric bit for bit, so its sums
+    serve as well), the loss-only call when neither does.  backward() multiplies by the upstream coefficient of each map
+    value."""
+
+    @staticmethod
+    def forward(ctx, img1, img2, window_size, size_average):
+        x, y = _f32c(img1), _f32c(img2)
+        B, C, H, W = x.shape
+        need1, need2 = bool(ctx.needs_input_grad[0]), bool(ctx.needs_input_grad[1])
+        # the map is the same bits with the images exchanged, so whichever call runs supplies the sums: one tile pass per
+        # gradient wanted, the loss-only pass when none is
+        g1 = g2 = None
+        if need1 or not need2:
+            sums, g1 = _ssim_sums(x, y, window_size, need1)
+        if need2:
+            swapped, g2 = _ssim_sums(y, x, window_size, True)
+            sums = sums if need1 else swapped
+        ctx.save_for_backward(*(g for g in (g1, g2) if g is not None))
+        ctx.has, ctx.size_average, ctx.dtypes = (need1, need2), bool(size_average), (img1.dtype, img2.dtype)
+        if size_average:
+            return (sums[B] / float(B * C * H * W)).to(torch.float32)
+        return (sums[:B] / float(C * H * W)).to(torch.float32)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gout):
+        saved = list(ctx.saved_tensors)
+        ref = saved[0]
+        B, C, H, W = ref.shape
+        gout = gout.to(torch.float32)
+        coef = gout.reshape(()) / float(B * C * H * W) if ctx.size_average else gout.reshape(B, 1, 1, 1) / float(C * H * W)
+        out = [None, None]
+        for i in (0, 1):
+            if ctx.has[i]:
+                out[i] = (saved.pop(0) * coef).to(ctx.dtypes[i])
+        return out[0], out[1], None, None
+
+
+def ssim_loss(img1, img2, window_size=11, size_average=True):
+    """loss_ssim.py's ssim(img1, img2, window_size, size_average): the mean of the SSIM map under the window_size^2
+    Gaussian window ('same', zero padding), a scalar, or (B,) per-image means with size_average=False; fp32 whatever the
+    floating dtype of the inputs, differentiable once with respect to either image or both."""
+    _need_gpu(img1, img2)
+    if img1.dim() != 4 or img1.shape != img2.shape:
+        raise ValueError(f"ssl_amd: ssim takes two (B,C,H,W) images of one shape, got {tuple(img1.shape)} and "
+                         f"{tuple(img2.shape)}")
+    if not img1.dtype.is_floating_point or not img2.dtype.is_floating_point:
+        raise ValueError(f"ssl_amd: ssim takes floating tensors, got {img1.dtype} and {img2.dtype}")
+    if img1.numel() == 0:
+        raise ValueError(f"ssl_amd: an empty tensor of shape {tuple(img1.shape)} holds no image")
+    return _SSIMFn.apply(img1, img2, check_ssim_window(window_size), size_average)
+
+
+def check_ssim_window(window_size):
+    """The window sizes the kernels run: odd, 1 .. 11 (a smaller window is the 11-tap kernel with zero taps)."""
+    if window_size != int(window_size) or int(window_size) < 1:
+        raise ValueError(f"ssl_amd: window_size must be a positive integer, got {window_size!r}")
+    window_size = int(window_size)
+    if window_size % 2 == 0:
+        raise ValueError(f"ssl_amd: SSIM runs odd window sizes up to {SSIM_MAX_WINDOW} only, got {window_size} (the "
+                         "reference's even sizes change the output shape)")
+    if window_size > SSIM_MAX_WINDOW:
+        raise ValueError(f"ssl_amd: SSIM runs odd window sizes up to {SSIM_MAX_WINDOW} only, got {window_size}")
+    return window_size

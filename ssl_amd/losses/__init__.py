@@ -2,3 +2,4 @@ from .basic_loss import ArtifactLoss, KLDistanceLoss, L1Loss, SSGLoss, set_nativ
 from .loss_util import get_artifact_map, get_local_weights, get_refined_artifact_map, similarity_map  # noqa: F401
 from .lazy import LazySSG, lazy_enabled, set_lazy  # noqa: F401
 from .bebygan import BBL, BackProjectionLoss, BestBuddyLoss, get_flat_mask, imresize  # noqa: F401
+from .ssim import SSIMLoss, create_window, gaussian, ssim  # noqa: F401
