@@ -128,6 +128,7 @@ static bool stream_capturing(hipStream_t st) {
 struct PlanHint {
   int *host = nullptr, *dev = nullptr;
 };
+constexpr bool NEVER_ALLOCATE = true;   // (plan_hint: a reader's call)
 static PlanHint plan_hint(bool allocate_never = false) {
   static std::mutex mu;
   static PlanHint tab[MAXDEV];
@@ -188,13 +189,14 @@ struct Schedule {
 // written by the GPU asynchronously, and decisions taken from two reads could disagree (a flip between them could record
 // a gated pair into a capturing stream).  `chains`: the call can run two chains (a fused step with a gradient and a plan;
 // a loss backward, whose split_backward checks the rest).
-static Schedule schedule(hipStream_t st, int ks, bool chains) {
+enum class Chains { never, possible };
+static Schedule schedule(hipStream_t st, int ks, Chains chains) {
   Schedule s;
   s.st = st;
   const int mode = overlap_mode();
   int n_sparse = -1, n_tiles = -1;
   if (mode == 3) {
-    const PlanHint h = plan_hint(true);   // (readers never allocate: the builder's launch does, outside capture)
+    const PlanHint h = plan_hint(NEVER_ALLOCATE);   // (readers never allocate: the builder's launch does, outside capture)
     if (h.host) {
       n_sparse = ((volatile int *)h.host)[0];
       n_tiles = ((volatile int *)h.host)[1];
@@ -211,7 +213,7 @@ static Schedule schedule(hipStream_t st, int ks, bool chains) {
   const bool free = mode == 3 && known && (direct_longer || n_tiles <= 512);
   // (under stream capture only free-running chains: they replay well -- C4 0.452 ms as a graph, 0.495 joined --, a
   // GATED pair does not: C2 as a graph 1.44 ms gated, 1.26 with fork / join around each pass, which it keeps)
-  s.chains = chains && s.may_fork && (free || !stream_capturing(st));
+  s.chains = chains == Chains::possible && s.may_fork && (free || !stream_capturing(st));
   s.gated = !free && s.assign == 1;   // (dense chain on the side stream -- a forced ssg_set_overlap(2): free-running)
   return s;
 }
@@ -298,10 +300,26 @@ static int bwd_qsplit() {   // 0 = chosen on the device from the number of dense
   return v;
 }
 
-// Scratch of the split backward (ssg_grad_rows -> dense-tile kernel + direct kernel): G (n, k_s^2), sum_b (n).
-static size_t split_scratch_bytes(int n_rows, int ks) {
-  const size_t n = (size_t)(n_rows > 0 ? n_rows : 1);
-  return align_up(sizeof(float) * n * ks * ks, 256) + 3 * align_up(sizeof(float) * n, 256);   // G, sum_b, max|G| parts, dot
+// a capacity as the sizes below count it: room for one row at least
+static size_t rows_of(int capacity) { return (size_t)(capacity > 0 ? capacity : 1); }
+
+// Scratch of the split backward (ssg_grad_rows -> dense-tile kernel + direct kernel), carved in one place: the sizes
+// (ssg_backward_scratch_bytes, ssg_loss_scratch_bytes), split_backward and loss_backward use it.  GRAD_LOSS: a loss step's
+// scratch, which has the criteria sums' partials in front (none of B, H, W is looked at otherwise).
+struct BackwardScratch {
+  size_t partials, G, sum_b, gmax_part, dot, end;
+};
+static BackwardScratch carve_backward_scratch(int B, int H, int W, int n_rows, int ks, GradMode mode) {
+  const size_t n = rows_of(n_rows);
+  BackwardScratch s{};
+  Carver c;
+  s.partials = c.take(mode == GRAD_LOSS ? 2 * sizeof(float) * bwd_max_partials(B, H, W, n_rows) + 64 : 0);
+  s.G = c.take(sizeof(float) * n * ks * ks);   // (n, k_s^2)
+  s.sum_b = c.take(sizeof(float) * n);         // (n)
+  s.gmax_part = c.take(sizeof(float) * n);     // max|G| parts
+  s.dot = c.take(sizeof(float) * n);
+  s.end = c.end;
+  return s;
 }
 
 // Tile-major scratch rows of the fused step at k_s = 49 (TmRowsParams, ssg_common.hpp): the dense tiles in the first
@@ -322,11 +340,174 @@ static bool tile_major_enabled() {
   return on;
 }
 
+// One description of an entry-point call: what the map, loss and operator entry points are given, under one set of
+// names.  Each entry point fills it once; map_forward_impl, loss_backward, split_backward and the functions that build
+// the kernels' parameter structs below read it (with the call's Schedule, which holds the streams).  The operator is a
+// call with (Y, X) positions (estride 2), one image, raw output and sigma 1.
+struct Call {
+  const float *img = nullptr, *img2 = nullptr;   // (B,C,H,W): the image (sr); the second image of a forward (gt)
+  int B = 0, C = 0, H = 0, W = 0;
+  const int *edges = nullptr;
+  int estride = 3;                 // 3: (b,y,x) rows of an edge list; 2: the operator's (Y,X) positions
+  const int *order = nullptr;      // nullable: tile-major order of the rows
+  const int *rank = nullptr;       // nullable: rank map (with plan: the dense-tile kernels)
+  const int *plan = nullptr;       // nullable: forward plan
+  const int *n_dev = nullptr;      // nullable: the device's row count
+  int n_rows = 0;                  // the host's bound on the rows
+  int ks = 0, kw = 0;
+  float sigma = 1.f, eps = 0.f;
+  int generalization = 0;
+  int raw = 0;                     // 1: the reference operator's forward (out += D)
+  float w_l1 = 0.f, w_kl = 0.f;
+  const float *upstream = nullptr;   // nullable device {dL/dl1, dL/dkl}
+  float *ssg = nullptr, *ssg2 = nullptr;   // the SSG tensors (forward: outputs; GRAD_S: S saved; GRAD_LOSS: S_sr, S_gt)
+  const float *gin = nullptr;      // GRAD_D: dL/dD; GRAD_S: dL/dS
+  float *loss_out = nullptr;
+  float *grad = nullptr;           // nullable in a loss call: loss only
+  void *grad_fix = nullptr;        // nullable: deterministic mode (grad_fix_bytes)
+  double *row_scale = nullptr;     // nullable: deferred normalisation (written by the dense forward, read by the row passes)
+  void *scratch = nullptr;         // the backward's scratch (BackwardScratch)
+  TileMajor tm;                    // the tile-major regions (slots 0: none)
+  bool row_scale_zeroed = false;   // the row scales were cleared by the edge-list builder's first kernel
+  bool rows_scratch = false;       // the SSG tensors are the engine's own scratch: nothing is written back
+  bool fix_zeroed = false;         // the fixed-point sums were cleared by the edge-list builder's first kernel
+  bool grad_is_output = false;     // the gradient is an OUTPUT of the call: the deterministic flush assigns it (fp32 atomics: cleared first)
+  bool nan_on_overflow = false;    // the loss finalize / tiny step report an overflowed edge list as NaN
+};
+
+// The checks of the map and loss entry points, in the order the ABI documents: bad sizes, then an image too small for
+// reflect padding, then "nothing to do" (a loss call zero-fills loss_out), then the null checks of the kind of call.
+// true: the call ends here with `rc`.
+enum CallKind { MAP_FORWARD, MAP_BACKWARD, LOSS_BACKWARD };
+static bool call_ends(const Call &c, CallKind kind, hipStream_t st, int &rc) {
+  rc = SSG_E_BADARG;
+  if (c.n_rows < 0 || !sizes_ok(c.ks, c.kw) || c.B <= 0 || c.C <= 0 || (kind == LOSS_BACKWARD && !c.loss_out)) return true;
+  rc = SSG_E_IMAGESMALL;
+  if (c.H <= c.ks / 2 || c.W <= c.ks / 2) return true;
+  if (c.n_rows == 0) {
+    rc = kind == LOSS_BACKWARD ? (int)hipMemsetAsync(c.loss_out, 0, 2 * sizeof(float), st) : 0;
+    return true;
+  }
+  rc = SSG_E_BADARG;
+  if (!c.img || !c.edges || !c.ssg) return true;
+  switch (kind) {
+    case MAP_FORWARD: return (c.img2 != nullptr) != (c.ssg2 != nullptr);
+    case MAP_BACKWARD: return !c.gin || !c.grad;
+    case LOSS_BACKWARD: return !c.ssg2 || !c.scratch;
+  }
+  return true;
+}
+
+// ---- the kernels' parameter structs (ssg_common.hpp), each value-initialised and filled in ONE function ----
+static FwdParams fwd_params(const Call &c) {
+  FwdParams p{};
+  p.img[0] = c.img;
+  p.img[1] = c.img2;
+  p.out[0] = c.ssg;
+  p.out[1] = c.ssg2;
+  p.nimg = c.img2 ? 2 : 1;
+  p.edges = c.edges;
+  p.estride = c.estride;
+  p.order = c.order;
+  p.n_dev = c.n_dev;
+  p.n_host = c.n_rows;
+  p.B = c.B;
+  p.C = c.C;
+  p.H = c.H;
+  p.W = c.W;
+  p.sigma = c.sigma;
+  p.eps = c.eps;
+  p.generalization = c.generalization;
+  p.raw = c.raw;
+  p.ks = c.ks;
+  p.kw = c.kw;
+  p.dbg = dbg_mask() & 0xff;
+  return p;
+}
+
+// dense tiles -> shared-term kernel (the operator: in raw mode)
+static DenseParams dense_params(const Call &c, const PlanView &pv) {
+  DenseParams d{};
+  d.img[0] = c.img;
+  d.img[1] = c.img2;
+  d.out[0] = c.ssg;
+  d.out[1] = c.ssg2;
+  d.nimg = c.img2 ? 2 : 1;
+  d.rank = c.rank;
+  d.n_dense = pv.dense_hdr;
+  d.tiles = pv.tiles;
+  d.max_tiles = dense_max_tiles(c.B, c.H, c.W, c.ks);
+  d.n_dev = c.n_dev;
+  d.n_host = c.n_rows;
+  d.B = c.B;
+  d.H = c.H;
+  d.W = c.W;
+  d.sigma = c.sigma;
+  d.eps = c.eps;
+  d.generalization = c.generalization;
+  d.dbg = (dbg_mask() >> 16) & 0xff;
+  d.row_scale = c.row_scale;
+  d.status = device_status_word();
+  d.raw = c.raw;
+  if (c.tm.slots > 0 && c.row_scale && c.img2) {
+    d.tm[0] = c.tm.rows[0];
+    d.tm[1] = c.tm.rows[1];
+    d.tm_slots = c.tm.slots;
+    d.max_strips = strips_enabled() ? dense_max_strips(c.B, c.H, c.W, c.ks) : 0;   // (k_s 49: whole strips of heavy tiles)
+    d.strips = d.max_strips ? pv.strips : nullptr;
+  }
+  return d;
+}
+
+// The three gradient modes differ only in which sources they set.  Deterministic mode: the kernels add into the
+// caller's zeroed fixed-point buffer (det_begin), one flush folds it into grad (det_end).
+static BwdParams bwd_params(const Call &c, GradMode mode) {
+  BwdParams p{};
+  p.img = c.img;
+  p.grad = c.grad;
+  p.gfix = c.grad_fix && c.grad ? (long long *)c.grad_fix : nullptr;
+  p.edges = c.edges;
+  p.estride = c.estride;
+  p.order = c.order;
+  p.n_dev = c.n_dev;
+  p.n_host = c.n_rows;
+  p.B = c.B;
+  p.C = c.C;
+  p.H = c.H;
+  p.W = c.W;
+  p.mode = mode;
+  p.sigma = c.sigma;
+  p.generalization = c.generalization;
+  p.ks = c.ks;
+  p.kw = c.kw;
+  p.dbg = (dbg_mask() >> 8) & 0xff;
+  switch (mode) {
+    case GRAD_D:
+      p.gin = c.gin;
+      break;
+    case GRAD_S:
+      p.gin = c.gin;
+      p.ssg = c.ssg;
+      break;
+    case GRAD_LOSS:
+      p.ssg = c.ssg;
+      p.ssg2 = c.ssg2;
+      p.w_l1 = c.w_l1;
+      p.w_kl = c.w_kl;
+      p.upstream = c.upstream;
+      p.row_scale = c.row_scale;
+      p.rows_scratch = c.rows_scratch ? 1 : 0;
+      p.partials = (float *)((char *)c.scratch + carve_backward_scratch(c.B, c.H, c.W, c.n_rows, c.ks, mode).partials);
+      break;
+  }
+  return p;
+}
+
 // nparts of a split backward's criteria sums: ssg_grad_rows' workgroups, then ssg_rows_tm's
-static int split_tm_tiles(const BwdParams &p, const TileMajor *tm) {
-  if (!tm || tm->slots <= 0) return 0;
+static int split_tm_tiles(const BwdParams &p, const TileMajor &tm) {
+  if (tm.slots <= 0) return 0;
   const int mt = dense_max_tiles(p.B, p.H, p.W, p.ks);
-  return tm->slots < mt ? tm->slots : mt;
+  return tm.slots < mt ? tm.slots : mt;
 }
 
 // per-class row passes (split_backward): the criteria sums then take two sets of grow_grid(n_rows) slots
@@ -334,20 +515,18 @@ static bool split_row_classes(const BwdParams &p, int n_tm) {
   return p.mode == GRAD_LOSS && n_tm == 0 && p.row_scale && p.ks <= 25;
 }
 
-// Backward over a forward plan: G rows (+ criteria sums) by ssg_grad_rows, the dense tiles by the shared-term
-// kernel, the remaining rows by the direct kernel in GRAD_D mode.  `p` carries the sources as for launch_bwd.  `fin`
-// (with `fin_done`): the loss finalize of a GRAD_LOSS step, launched here where the schedule has a place for it off
-// the critical path.  Joins the call's fork behind the backward kernels.
-static int split_backward(BwdParams p, const int *rank, const int *plan, void *scratch, Schedule &sc,
-                          const LossFinalize *fin = nullptr, bool *fin_done = nullptr, const TileMajor *tm = nullptr) {
-  const hipStream_t st = sc.st;
-  float *G = (float *)scratch;
-  const size_t nfl = align_up(sizeof(float) * (size_t)(p.n_host > 0 ? p.n_host : 1), 256);
-  float *sum_b = (float *)((char *)scratch + align_up(sizeof(float) * (size_t)p.n_host * p.ks * p.ks, 256));
-  float *gmax_part = (float *)((char *)sum_b + nfl);
-  float *dot = (float *)((char *)gmax_part + nfl);
-  const int n_tm = split_tm_tiles(p, tm);
-  const PlanView pv = plan_view(plan, p.B, p.H, p.W);
+// What split_backward adds to a call's BwdParams for its three kernels: the pieces of the scratch, the plan's parts,
+// the tile-major regions in use and where the fixed-point scale comes from.
+struct SplitParts {
+  float *G, *sum_b, *gmax_part, *dot;
+  PlanView pv;
+  const int *rank;
+  const TileMajor *tm;
+  int n_tm;           // tile-major tiles of the call (split_tm_tiles; 0: row-major rows only)
+  bool apriori;       // the fixed-point scale comes from the a-priori bound of |G|
+};
+
+static GrowParams grow_params(const BwdParams &p, const SplitParts &x) {
   GrowParams g{};
   g.mode = p.mode;
   g.gin = p.gin;
@@ -363,99 +542,65 @@ static int split_backward(BwdParams p, const int *rank, const int *plan, void *s
   g.w_l1 = p.w_l1;
   g.w_kl = p.w_kl;
   g.upstream = p.upstream;
-  g.G = p.grad ? G : nullptr;
-  g.sum_b = p.grad ? sum_b : nullptr;
+  g.G = p.grad ? x.G : nullptr;
+  g.sum_b = p.grad ? x.sum_b : nullptr;
   g.partials = p.partials;
-  g.gmax_part = p.gfix ? gmax_part : nullptr;
-  if (n_tm > 0) {   // (tile-major call: ssg_grad_rows walks the plan's list of sparse rows with a capped grid)
+  g.gmax_part = p.gfix ? x.gmax_part : nullptr;
+  if (x.n_tm > 0) {   // (tile-major call: ssg_grad_rows walks the plan's list of sparse rows with a capped grid)
     g.grid_cap = 4096;
-    g.tm_hdr = pv.dense_hdr;
-    g.tm_slots = tm->slots;
-    g.sparse_order = pv.sparse_order;
+    g.tm_hdr = x.pv.dense_hdr;
+    g.tm_slots = x.tm->slots;
+    g.sparse_order = x.pv.sparse_order;
   }
-  // GRAD_LOSS without tile-major rows (every k_s <= 25 call): the fixed-point scale comes from the a-priori bound of |G|
-  // (ssg_grad_rows' first workgroup writes it: no maximum over the rows, no reduction launch); and with deferred row
-  // scales the rows are passed over PER CLASS -- the dense-tile kernels' rows (non-zero scale), then the plan's sparse
-  // list -- whatever the schedule, so that the criteria sums are grouped the same way on one stream and on two.
-  const size_t n_fix = (size_t)p.B * p.C * p.H * p.W;
-  const bool apriori = p.gfix && p.mode == GRAD_LOSS && n_tm == 0;
-  const bool classes = split_row_classes(p, n_tm);
-  // A backward on its own (ssg_loss_backward: the deferred loop's node, the module) forks HERE and runs the same two
-  // chains from the row passes on: the sparse list's pass beside the dense-tile rows' instead of behind it.
-  if (sc.chains && !sc.open && classes && p.grad) fork_side(sc, dbg_mask() & ((1 << 27) | (1 << 28) | (1 << 29)));
-  // Gated chains: the direct backward is released once the dense FORWARD is through and runs beside the memory-bound
-  // dense row pass -- C2 1.1996 -> 1.178 ms against a release behind that row pass, three alternations
-  // (profiles/r6_schedule_ab.txt; holding the direct FORWARD until the dense forward is through as well: 1.184 alone,
-  // 1.20 together).  The loss finalize follows the direct backward on its stream, behind a second event for the dense
-  // chain's row pass.
-  const bool gated = sc.open && sc.gated;
-  if (apriori) {
+  if (x.apriori) {   // (ssg_grad_rows' first workgroup writes the bound into the word behind the fixed-point sums)
     g.gmax_part = nullptr;
-    g.fix_word = (unsigned *)(p.gfix + n_fix);
+    g.fix_word = (unsigned *)(p.gfix + (size_t)p.B * p.C * p.H * p.W);
   }
-  int rc = gated ? (int)hipEventRecord(sc.side->gate, st) : 0;   // (behind the dense forward, in front of its row pass)
-  if (!rc && !(dbg_mask() & (1 << 29))) {
-    if (classes) {
-      GrowParams gd = g;   // the dense-tile rows
-      gd.only = 1;
-      rc = launch_grad_rows(gd, p.ks, p.kw, sc.dense());
-      GrowParams gs = g;   // the plan's sparse list; its criteria sums behind the first pass's
-      gs.only = 2;
-      gs.grid_cap = 4096;
-      gs.tm_hdr = pv.dense_hdr;
-      gs.tm_slots = 0;
-      gs.sparse_order = pv.sparse_order;
-      gs.partials = p.partials + 2 * (size_t)grow_grid(p.n_host);
-      if (!rc) rc = launch_grad_rows(gs, p.ks, p.kw, sc.direct());
-    } else {
-      rc = launch_grad_rows(g, p.ks, p.kw, st);
-    }
+  return g;
+}
+
+// the rows of the tile-major tiles (ssg_grad_rows skips them: negative row scale)
+static TmRowsParams tm_rows_params(const BwdParams &p, const SplitParts &x) {
+  TmRowsParams t{};
+  t.tm[0] = x.tm->rows[0];
+  t.tm[1] = x.tm->rows[1];
+  t.row_scale = p.row_scale;
+  t.rank = x.rank;
+  t.n_dense = x.pv.dense_hdr;
+  t.tiles = x.pv.tiles;
+  t.n_tiles = x.n_tm;
+  t.tm_slots = x.tm->slots;
+  t.n_dev = p.n_dev;
+  t.n_host = p.n_host;
+  t.B = p.B;
+  t.H = p.H;
+  t.W = p.W;
+  t.C = p.C;
+  t.sigma = p.sigma;
+  t.w_l1 = p.w_l1;
+  t.w_kl = p.w_kl;
+  t.upstream = p.upstream;
+  t.dot = x.dot;
+  t.sum_b = x.sum_b;
+  t.partials = p.partials + 2 * (size_t)grow_grid(p.n_host);
+  t.gmax_part = p.gfix ? x.gmax_part + grow_grid(p.n_host) : nullptr;
+  if (!p.rows_scratch) {   // materialising call: the normalised rows of the tile-major tiles are written here
+    t.out[0] = p.ssg;
+    t.out[1] = p.ssg2;
   }
-  if (!rc && n_tm > 0) {   // the rows of the tile-major tiles (ssg_grad_rows skipped them: negative row scale)
-    TmRowsParams t{};
-    t.tm[0] = tm->rows[0];
-    t.tm[1] = tm->rows[1];
-    t.row_scale = p.row_scale;
-    t.rank = rank;
-    t.n_dense = pv.dense_hdr;
-    t.tiles = pv.tiles;
-    t.n_tiles = n_tm;
-    t.tm_slots = tm->slots;
-    t.n_dev = p.n_dev;
-    t.n_host = p.n_host;
-    t.B = p.B;
-    t.H = p.H;
-    t.W = p.W;
-    t.C = p.C;
-    t.sigma = p.sigma;
-    t.w_l1 = p.w_l1;
-    t.w_kl = p.w_kl;
-    t.upstream = p.upstream;
-    t.dot = dot;
-    t.sum_b = sum_b;
-    t.partials = p.partials + 2 * (size_t)grow_grid(p.n_host);
-    t.gmax_part = p.gfix ? gmax_part + grow_grid(p.n_host) : nullptr;
-    if (!p.rows_scratch) {   // materialising call: the normalised rows of the tile-major tiles are written here
-      t.out[0] = p.ssg;
-      t.out[1] = p.ssg2;
-    }
-    rc = (dbg_mask() & (1 << 29)) ? 0 : launch_rows_tm(t, p.ks, p.kw, st);
-  }
-  if (rc || !p.grad) return rc;   // (two chains still forked: the entry point joins them)
-  if (p.gfix && !apriori) {
-    rc = launch_grad_fix_reduce(gmax_part, (int)grow_grid(p.n_host) + rows_tm_parts(n_tm), p.gfix, n_fix, st);
-    if (rc) return rc;
-  }
-  const float *grows = p.mode == GRAD_D ? p.gin : G;
+  return t;
+}
+
+static DenseBwdParams dense_bwd_params(const BwdParams &p, const SplitParts &x) {
   DenseBwdParams d{};
   d.img = p.img;
   d.grad = p.grad;
   d.gfix = p.gfix;
-  d.G = grows;
-  d.sum_b = sum_b;
-  d.rank = rank;
-  d.n_dense = pv.dense_hdr;
-  d.tiles = pv.tiles;
+  d.G = p.mode == GRAD_D ? p.gin : x.G;   // (GRAD_D: the caller's rows ARE the G rows)
+  d.sum_b = x.sum_b;
+  d.rank = x.rank;
+  d.n_dense = x.pv.dense_hdr;
+  d.tiles = x.pv.tiles;
   d.max_tiles = dense_max_tiles(p.B, p.H, p.W, p.ks);
   d.n_dev = p.n_dev;
   d.n_host = p.n_host;
@@ -465,17 +610,110 @@ static int split_backward(BwdParams p, const int *rank, const int *plan, void *s
   d.qsplit = bwd_qsplit();
   d.dbg = p.dbg;
   d.status = device_status_word();
-  if (n_tm > 0) {
-    d.tm[0] = tm->rows[0];
-    d.tm[1] = tm->rows[1];
+  if (x.n_tm > 0) {
+    d.tm[0] = x.tm->rows[0];
+    d.tm[1] = x.tm->rows[1];
     d.row_scale = p.row_scale;
-    d.dot = dot;
-    d.tm_slots = tm->slots;
+    d.dot = x.dot;
+    d.tm_slots = x.tm->slots;
     d.sigma = p.sigma;
     d.w_l1 = p.w_l1;
     d.w_kl = p.w_kl;
     d.upstream = p.upstream;
   }
+  return d;
+}
+
+// the fused step of a small (11,5) call; `ticket`: the word tiny_edge_list zeroed
+static TinyParams tiny_params(const Call &c, int *ticket) {
+  TinyParams t{};
+  t.img[0] = c.img;
+  t.img[1] = c.img2;
+  t.out[0] = c.rows_scratch ? nullptr : c.ssg;
+  t.out[1] = c.rows_scratch ? nullptr : c.ssg2;
+  t.edges = c.edges;
+  t.n_dev = c.n_dev;
+  t.n_host = c.n_rows;
+  t.B = c.B;
+  t.H = c.H;
+  t.W = c.W;
+  t.sigma = c.sigma;
+  t.eps = c.eps;
+  t.generalization = c.generalization;
+  t.w_l1 = c.w_l1;
+  t.w_kl = c.w_kl;
+  t.grad = c.grad;
+  t.gfix = c.grad_fix && c.grad ? (long long *)c.grad_fix : nullptr;
+  t.assign = c.grad_is_output ? 1 : 0;
+  t.partials = (float *)c.scratch;
+  t.loss_out = c.loss_out;
+  t.ticket = ticket;
+  t.nan_on_overflow = c.nan_on_overflow ? 1 : 0;
+  t.dbg = env_int("SSG_TINY_DBG", 0);
+  return t;
+}
+
+// Backward over a forward plan: G rows (+ criteria sums) by ssg_grad_rows, the dense tiles by the shared-term
+// kernel, the remaining rows by the direct kernel in GRAD_D mode.  `p` carries the call's sources as for launch_bwd.
+// `fin` (with `fin_done`): the loss finalize of a GRAD_LOSS step, launched here where the schedule has a place for it
+// off the critical path.  Joins the call's fork behind the backward kernels.
+static int split_backward(const Call &c, const BwdParams &p, Schedule &sc, const LossFinalize *fin = nullptr,
+                          bool *fin_done = nullptr) {
+  const hipStream_t st = sc.st;
+  const BackwardScratch bs = carve_backward_scratch(p.B, p.H, p.W, p.n_host, p.ks, (GradMode)p.mode);
+  char *const scratch = (char *)c.scratch;
+  SplitParts x{};
+  x.G = (float *)(scratch + bs.G);
+  x.sum_b = (float *)(scratch + bs.sum_b);
+  x.gmax_part = (float *)(scratch + bs.gmax_part);
+  x.dot = (float *)(scratch + bs.dot);
+  x.pv = plan_view(c.plan, p.B, p.H, p.W);
+  x.rank = c.rank;
+  x.tm = &c.tm;
+  x.n_tm = split_tm_tiles(p, c.tm);
+  const int n_tm = x.n_tm;
+  // GRAD_LOSS without tile-major rows (every k_s <= 25 call): the fixed-point scale comes from the a-priori bound of |G|
+  // (ssg_grad_rows' first workgroup writes it: no maximum over the rows, no reduction launch); and with deferred row
+  // scales the rows are passed over PER CLASS -- the dense-tile kernels' rows (non-zero scale), then the plan's sparse
+  // list -- whatever the schedule, so that the criteria sums are grouped the same way on one stream and on two.
+  const size_t n_fix = (size_t)p.B * p.C * p.H * p.W;
+  x.apriori = p.gfix && p.mode == GRAD_LOSS && n_tm == 0;
+  const bool classes = split_row_classes(p, n_tm);
+  const GrowParams g = grow_params(p, x);
+  // A backward on its own (ssg_loss_backward: the deferred loop's node, the module) forks HERE and runs the same two
+  // chains from the row passes on: the sparse list's pass beside the dense-tile rows' instead of behind it.
+  if (sc.chains && !sc.open && classes && p.grad) fork_side(sc, dbg_mask() & ((1 << 27) | (1 << 28) | (1 << 29)));
+  // Gated chains: the direct backward is released once the dense FORWARD is through and runs beside the memory-bound
+  // dense row pass -- C2 1.1996 -> 1.178 ms against a release behind that row pass, three alternations
+  // (profiles/r6_schedule_ab.txt; holding the direct FORWARD until the dense forward is through as well: 1.184 alone,
+  // 1.20 together).  The loss finalize follows the direct backward on its stream, behind a second event for the dense
+  // chain's row pass.
+  const bool gated = sc.open && sc.gated;
+  int rc = gated ? (int)hipEventRecord(sc.side->gate, st) : 0;   // (behind the dense forward, in front of its row pass)
+  if (!rc && !(dbg_mask() & (1 << 29))) {
+    if (classes) {
+      GrowParams gd = g;   // the dense-tile rows
+      gd.only = 1;
+      rc = launch_grad_rows(gd, p.ks, p.kw, sc.dense());
+      GrowParams gs = g;   // the plan's sparse list; its criteria sums behind the first pass's
+      gs.only = 2;
+      gs.grid_cap = 4096;
+      gs.tm_hdr = x.pv.dense_hdr;
+      gs.tm_slots = 0;
+      gs.sparse_order = x.pv.sparse_order;
+      gs.partials = p.partials + 2 * (size_t)grow_grid(p.n_host);
+      if (!rc) rc = launch_grad_rows(gs, p.ks, p.kw, sc.direct());
+    } else {
+      rc = launch_grad_rows(g, p.ks, p.kw, st);
+    }
+  }
+  if (!rc && n_tm > 0) rc = (dbg_mask() & (1 << 29)) ? 0 : launch_rows_tm(tm_rows_params(p, x), p.ks, p.kw, st);
+  if (rc || !p.grad) return rc;   // (two chains still forked: the entry point joins them)
+  if (p.gfix && !x.apriori) {
+    rc = launch_grad_fix_reduce(x.gmax_part, (int)grow_grid(p.n_host) + rows_tm_parts(n_tm), p.gfix, n_fix, st);
+    if (rc) return rc;
+  }
+  const DenseBwdParams d = dense_bwd_params(p, x);
   if (gated) {   // the direct backward waits for the dense FORWARD only; the finalize, behind it, for the dense row pass
     rc = (int)hipStreamWaitEvent(sc.direct(), sc.side->gate, 0);
     if (!rc) rc = (int)hipEventRecord(sc.side->gate2, sc.dense());
@@ -494,9 +732,9 @@ static int split_backward(BwdParams p, const int *rank, const int *plan, void *s
   if (!rc && !(dbg_mask() & (1 << 28))) {
     BwdParams s = p;
     s.mode = GRAD_D;
-    s.gin = grows;
-    s.order = pv.sparse_order;
-    s.n_dev = pv.n_sparse;
+    s.gin = d.G;
+    s.order = x.pv.sparse_order;
+    s.n_dev = x.pv.n_sparse;
     s.partials = nullptr;
     s.rows_hint = sc.rows_hint;
     rc = launch_bwd(s, sc.direct());
@@ -513,16 +751,13 @@ static int split_backward(BwdParams p, const int *rank, const int *plan, void *s
 // Deterministic mode: the kernels add into the caller's zeroed fixed-point buffer; one flush folds it into grad.
 // the fixed-point gradient sums of a (B,C,H,W) image and, behind them, the word with the bound of |G| (8 sums' room)
 static size_t grad_fix_bytes(int B, int C, int H, int W) { return sizeof(long long) * ((size_t)B * C * H * W + 8); }
-static int det_begin(BwdParams &p, void *grad_fix, hipStream_t st, bool prezeroed = false) {
-  p.gfix = nullptr;
-  if (!grad_fix || !p.grad) return 0;
-  p.gfix = (long long *)grad_fix;
-  if (prezeroed) return 0;   // (the fused step: cleared by the edge-list builder's first kernel)
-  return (int)hipMemsetAsync(grad_fix, 0, grad_fix_bytes(p.B, p.C, p.H, p.W), st);
+static int det_begin(const Call &c, const BwdParams &p, hipStream_t st) {
+  if (!p.gfix || c.fix_zeroed) return 0;   // (the fused step: cleared by the edge-list builder's first kernel)
+  return (int)hipMemsetAsync(p.gfix, 0, grad_fix_bytes(p.B, p.C, p.H, p.W), st);
 }
-static int det_end(const BwdParams &p, hipStream_t st, bool assign = false, const LossFinalize *fin = nullptr, bool *fin_done = nullptr) {
+static int det_end(const Call &c, const BwdParams &p, hipStream_t st, const LossFinalize *fin = nullptr, bool *fin_done = nullptr) {
   if (!p.gfix) return 0;
-  const int rc = launch_grad_fix_flush(p.gfix, p.grad, (size_t)p.B * p.C * p.H * p.W, assign ? 1 : 0, st, fin);
+  const int rc = launch_grad_fix_flush(p.gfix, p.grad, (size_t)p.B * p.C * p.H * p.W, c.grad_is_output ? 1 : 0, st, fin);
   if (!rc && fin && fin_done) *fin_done = true;
   return rc;
 }
@@ -576,8 +811,9 @@ struct OpPlan {
 // true: the call qualifies for the plan path (enough positions, a size with shared-term kernels, not inside a stream capture)
 // (the forward gains less from the shared-term kernel than the backward -- measured at 18,417 positions: forward 0.196 ms
 // direct / 0.231 with the plan, backward 0.462 / 0.258 -- so it takes the plan from three times as many positions)
-static bool op_wants_plan(int mc, int ks, int kw, int C, hipStream_t st, bool forward) {
-  const long from = (long)op_plan_from() * (forward && op_plan_from() > 1 ? 3 : 1);
+enum OpPass { OP_FORWARD, OP_BACKWARD };
+static bool op_wants_plan(int mc, int ks, int kw, int C, hipStream_t st, OpPass pass) {
+  const long from = (long)op_plan_from() * (pass == OP_FORWARD && op_plan_from() > 1 ? 3 : 1);
   if (from >= 0x7fffffffL || (long)mc < from || !dense_supported(ks, kw, C) || !dense_bwd_supported(ks, kw, C) || !grow_supported(ks, kw)) return false;
   if (!stream_capturing(st)) return true;
   (void)hipGetLastError();
@@ -629,8 +865,8 @@ static int op_plan_free(OpPlan &o, hipStream_t st) {
   return rc;
 }
 
-static bool split_ok(int ks, int kw, int C, const int *rank, const int *plan, const void *scratch) {
-  return rank && plan && scratch && grow_supported(ks, kw) && dense_bwd_supported(ks, kw, C) &&
+static bool split_ok(const Call &c) {
+  return c.rank && c.plan && c.scratch && grow_supported(c.ks, c.kw) && dense_bwd_supported(c.ks, c.kw, c.C) &&
          !(dbg_mask() & (1 << 24));
 }
 
@@ -656,50 +892,32 @@ int ssg_compute_similarity(const float *image, const int *pos, float *out, int m
   if (mc < 0 || !sizes_ok(psize, ksize) || channel <= 0 || height <= 0 || width <= 0) return SSG_E_BADARG;
   if (mc == 0) return 0;
   if (!image || !pos || !out) return SSG_E_BADARG;
-  FwdParams p{};
-  p.img[0] = image;
-  p.out[0] = out;
-  p.nimg = 1;
-  p.edges = pos;
-  p.estride = 2;
-  p.n_dev = nullptr;
-  p.n_host = mc;
-  p.B = 1;
-  p.C = channel;
-  p.H = height;
-  p.W = width;
-  p.sigma = 1.f;
-  p.eps = 0.f;
-  p.generalization = 0;
-  p.raw = 1;
-  p.ks = psize;
-  p.kw = ksize;
-  p.dbg = dbg_mask() & 0xff;
+  Call c;
+  c.img = image;
+  c.ssg = out;
+  c.edges = pos;
+  c.estride = 2;
+  c.n_rows = mc;
+  c.B = 1;
+  c.C = channel;
+  c.H = height;
+  c.W = width;
+  c.raw = 1;
+  c.ks = psize;
+  c.kw = ksize;
+  const FwdParams p = fwd_params(c);
   hipStream_t st = (hipStream_t)stream;
-  if (op_wants_plan(mc, psize, ksize, channel, st, true)) {
+  if (op_wants_plan(mc, psize, ksize, channel, st, OP_FORWARD)) {
     OpPlan o;
     int rc = op_plan_build(pos, mc, psize, height, width, 0, st, o);
     if (!rc && o.base) {
       // dense tiles -> shared-term kernel in raw mode, the rest (the plan's tile order, caller's row numbers) -> the
       // direct kernels, duplicates of a position -> a direct launch of their own
-      const PlanView pv = plan_view(o.plan, 1, height, width);
-      DenseParams d{};
-      d.img[0] = image;
-      d.out[0] = out;
-      d.nimg = 1;
-      d.rank = o.rank;
-      d.n_dense = pv.dense_hdr;
-      d.tiles = pv.tiles;
-      d.max_tiles = dense_max_tiles(1, height, width, psize);
-      d.n_host = mc;
-      d.B = 1;
-      d.H = height;
-      d.W = width;
-      d.sigma = 1.f;
-      d.raw = 1;
-      d.dbg = (dbg_mask() >> 16) & 0xff;
-      d.status = device_status_word();
-      Schedule sc = schedule(st, psize, false);
+      c.rank = o.rank;
+      c.plan = o.plan;
+      const PlanView pv = plan_view(c.plan, 1, height, width);
+      const DenseParams d = dense_params(c, pv);
+      Schedule sc = schedule(st, psize, Chains::never);
       fork_side(sc);
       rc = launch_fwd_dense(d, psize, ksize, channel, sc.dense());
       FwdParams q = p;
@@ -725,32 +943,32 @@ int ssg_compute_similarity_backward(const float *image, const float *grads, cons
   if (mc < 0 || !sizes_ok(psize, ksize) || channel <= 0 || height <= 0 || width <= 0) return SSG_E_BADARG;
   if (mc == 0) return 0;
   if (!image || !grads || !pos || !image_grads) return SSG_E_BADARG;
-  BwdParams p{};
-  p.img = image;
-  p.grad = image_grads;
-  p.edges = pos;
-  p.estride = 2;
-  p.n_dev = nullptr;
-  p.n_host = mc;
-  p.B = 1;
-  p.C = channel;
-  p.H = height;
-  p.W = width;
-  p.mode = GRAD_D;
-  p.gin = grads;
-  p.sigma = 1.f;
-  p.ks = psize;
-  p.kw = ksize;
-  p.dbg = (dbg_mask() >> 8) & 0xff;
+  Call c;
+  c.img = image;
+  c.grad = image_grads;
+  c.gin = grads;
+  c.edges = pos;
+  c.estride = 2;
+  c.n_rows = mc;
+  c.B = 1;
+  c.C = channel;
+  c.H = height;
+  c.W = width;
+  c.ks = psize;
+  c.kw = ksize;
+  const BwdParams p = bwd_params(c, GRAD_D);
   hipStream_t st = (hipStream_t)stream;
-  if (op_wants_plan(mc, psize, ksize, channel, st, false)) {
+  if (op_wants_plan(mc, psize, ksize, channel, st, OP_BACKWARD)) {
     OpPlan o;
-    int rc = op_plan_build(pos, mc, psize, height, width, split_scratch_bytes(mc, psize), st, o);
+    int rc = op_plan_build(pos, mc, psize, height, width, ssg_backward_scratch_bytes(mc, psize), st, o);
     if (!rc && o.base) {
       // the split backward in GRAD_D mode (`grads` ARE the G rows): border sums by ssg_grad_rows, dense tiles by the
       // shared-term kernel, the plan's sparse rows by the direct one; then the duplicates of a position on their own
-      Schedule sc = schedule(st, psize, false);
-      rc = split_backward(p, o.rank, o.plan, o.bscratch, sc);
+      c.rank = o.rank;
+      c.plan = o.plan;
+      c.scratch = o.bscratch;
+      Schedule sc = schedule(st, psize, Chains::never);
+      rc = split_backward(c, p, sc);
       BwdParams q = p;
       q.order = o.dup;
       q.n_dev = o.ndup;
@@ -794,74 +1012,20 @@ int ssg_edge_mask_laplacian(const float *gt, int B, int H, int W, float lap_thre
   return launch_edge_mask(gt, B, H, W, lap_threshold, mask_stride, mask_out, (hipStream_t)stream);
 }
 
-static int map_forward_impl(const float *img, const float *img2, int B, int C, int H, int W, const int *edges,
-                            const int *tile_order, const int *rank_map, const int *fwd_plan, const int *n_edges_dev,
-                            int n_rows, int ks, int kw, float sigma, float eps, int generalization, float *ssg,
-                            float *ssg2, double *row_scale, bool row_scale_zeroed, Schedule &sc,
-                            const TileMajor *tm = nullptr) {
-  if (n_rows < 0 || !sizes_ok(ks, kw) || B <= 0 || C <= 0) return SSG_E_BADARG;
-  if (H <= ks / 2 || W <= ks / 2) return SSG_E_IMAGESMALL;
-  if (n_rows == 0) return 0;
-  if (!img || !edges || !ssg || ((img2 != nullptr) != (ssg2 != nullptr))) return SSG_E_BADARG;
-  FwdParams p{};
-  p.img[0] = img;
-  p.img[1] = img2;
-  p.out[0] = ssg;
-  p.out[1] = ssg2;
-  p.nimg = img2 ? 2 : 1;
-  p.edges = edges;
-  p.estride = 3;
-  p.order = tile_order;
-  p.n_dev = n_edges_dev;
-  p.n_host = n_rows;
-  p.B = B;
-  p.C = C;
-  p.H = H;
-  p.W = W;
-  p.sigma = sigma;
-  p.eps = eps;
-  p.generalization = generalization;
-  p.raw = 0;
-  p.ks = ks;
-  p.kw = kw;
-  p.dbg = dbg_mask() & 0xff;
-  if (fwd_plan && rank_map && dense_supported(ks, kw, C)) {
+static int map_forward_impl(const Call &c, Schedule &sc) {
+  int rc = 0;
+  if (call_ends(c, MAP_FORWARD, sc.st, rc)) return rc;
+  FwdParams p = fwd_params(c);
+  if (c.plan && c.rank && dense_supported(c.ks, c.kw, c.C)) {
     // dense tiles -> shared-term kernel; the rest (plan's own tile-major order) -> direct kernels
-    const PlanView pv = plan_view(fwd_plan, B, H, W);
-    DenseParams d{};
-    d.img[0] = img;
-    d.img[1] = img2;
-    d.out[0] = ssg;
-    d.out[1] = ssg2;
-    d.nimg = p.nimg;
-    d.rank = rank_map;
-    d.n_dense = pv.dense_hdr;
-    d.tiles = pv.tiles;
-    d.max_tiles = dense_max_tiles(B, H, W, ks);
-    d.n_dev = n_edges_dev;
-    d.n_host = n_rows;
-    d.B = B;
-    d.H = H;
-    d.W = W;
-    d.sigma = sigma;
-    d.eps = eps;
-    d.generalization = generalization;
-    d.dbg = (dbg_mask() >> 16) & 0xff;
-    d.row_scale = row_scale;
-    d.status = device_status_word();
-    if (tm && tm->slots > 0 && row_scale && img2) {
-      d.tm[0] = tm->rows[0];
-      d.tm[1] = tm->rows[1];
-      d.tm_slots = tm->slots;
-      d.max_strips = strips_enabled() ? dense_max_strips(B, H, W, ks) : 0;   // (k_s 49: whole strips of heavy tiles)
-      d.strips = d.max_strips ? pv.strips : nullptr;
-    }
-    if (row_scale && !row_scale_zeroed) {   // 0 = "this row is already normalised" (the rows of the direct kernels)
-      const int rc0 = (int)hipMemsetAsync(row_scale, 0, sizeof(double) * 2 * (size_t)n_rows, sc.st);
+    const PlanView pv = plan_view(c.plan, c.B, c.H, c.W);
+    const DenseParams d = dense_params(c, pv);
+    if (c.row_scale && !c.row_scale_zeroed) {   // 0 = "this row is already normalised" (the rows of the direct kernels)
+      const int rc0 = (int)hipMemsetAsync(c.row_scale, 0, sizeof(double) * 2 * (size_t)c.n_rows, sc.st);
       if (rc0) return rc0;
     }
     fork_side(sc, dbg_mask() & ((1 << 25) | (1 << 26)));   // (ssg_set_overlap)
-    int rc = (dbg_mask() & (1 << 25)) ? 0 : launch_fwd_dense(d, ks, kw, C, sc.dense());
+    rc = (dbg_mask() & (1 << 25)) ? 0 : launch_fwd_dense(d, c.ks, c.kw, c.C, sc.dense());
     p.order = pv.sparse_order;
     p.n_dev = pv.n_sparse;
     p.rows_hint = sc.rows_hint;
@@ -877,115 +1041,100 @@ int ssg_map_forward(const float *img, const float *img2, int B, int C, int H, in
                     const int *tile_order, const int *rank_map, const int *fwd_plan, const int *n_edges_dev, int n_rows,
                     int ks, int kw, float sigma, float eps, int generalization, float *ssg, float *ssg2,
                     double *row_scale, ssg_stream_t stream) {
-  Schedule sc = schedule((hipStream_t)stream, ks, false);
-  return map_forward_impl(img, img2, B, C, H, W, edges, tile_order, rank_map, fwd_plan, n_edges_dev, n_rows, ks, kw,
-                          sigma, eps, generalization, ssg, ssg2, row_scale, false, sc);
+  Call c;
+  c.img = img;
+  c.img2 = img2;
+  c.B = B;
+  c.C = C;
+  c.H = H;
+  c.W = W;
+  c.edges = edges;
+  c.order = tile_order;
+  c.rank = rank_map;
+  c.plan = fwd_plan;
+  c.n_dev = n_edges_dev;
+  c.n_rows = n_rows;
+  c.ks = ks;
+  c.kw = kw;
+  c.sigma = sigma;
+  c.eps = eps;
+  c.generalization = generalization;
+  c.ssg = ssg;
+  c.ssg2 = ssg2;
+  c.row_scale = row_scale;
+  Schedule sc = schedule((hipStream_t)stream, ks, Chains::never);
+  return map_forward_impl(c, sc);
 }
 
-size_t ssg_backward_scratch_bytes(int n_rows, int ks) { return split_scratch_bytes(n_rows, ks); }
+size_t ssg_backward_scratch_bytes(int n_rows, int ks) { return carve_backward_scratch(0, 0, 0, n_rows, ks, GRAD_S).end; }
 
 int ssg_map_backward(const float *img, int B, int C, int H, int W, const int *edges, const int *tile_order,
                      const int *rank_map, const int *fwd_plan, const int *n_edges_dev, int n_rows, int ks, int kw,
                      float sigma, int generalization, const float *ssg, const float *grad_ssg, float *grad_img,
                      void *scratch, void *grad_fix, ssg_stream_t stream) {
-  if (n_rows < 0 || !sizes_ok(ks, kw) || B <= 0 || C <= 0) return SSG_E_BADARG;
-  if (H <= ks / 2 || W <= ks / 2) return SSG_E_IMAGESMALL;
-  if (n_rows == 0) return 0;
-  if (!img || !edges || !ssg || !grad_ssg || !grad_img) return SSG_E_BADARG;
-  BwdParams p{};
-  p.img = img;
-  p.grad = grad_img;
-  p.edges = edges;
-  p.estride = 3;
-  p.n_dev = n_edges_dev;
-  p.n_host = n_rows;
-  p.B = B;
-  p.C = C;
-  p.H = H;
-  p.W = W;
-  p.order = tile_order;
-  p.mode = GRAD_S;
-  p.gin = grad_ssg;
-  p.ssg = ssg;
-  p.sigma = sigma;
-  p.generalization = generalization;
-  p.ks = ks;
-  p.kw = kw;
-  p.dbg = (dbg_mask() >> 8) & 0xff;
-  int rc = det_begin(p, grad_fix, (hipStream_t)stream);
+  const hipStream_t st = (hipStream_t)stream;
+  Call c;
+  c.img = img;
+  c.B = B;
+  c.C = C;
+  c.H = H;
+  c.W = W;
+  c.edges = edges;
+  c.order = tile_order;
+  c.rank = rank_map;
+  c.plan = fwd_plan;
+  c.n_dev = n_edges_dev;
+  c.n_rows = n_rows;
+  c.ks = ks;
+  c.kw = kw;
+  c.sigma = sigma;
+  c.generalization = generalization;
+  c.ssg = const_cast<float *>(ssg);   // (GRAD_S: S saved, read only)
+  c.gin = grad_ssg;
+  c.grad = grad_img;
+  c.scratch = scratch;
+  c.grad_fix = grad_fix;
+  int rc = 0;
+  if (call_ends(c, MAP_BACKWARD, st, rc)) return rc;
+  const BwdParams p = bwd_params(c, GRAD_S);
+  rc = det_begin(c, p, st);
   if (rc) return rc;
-  if (split_ok(ks, kw, C, rank_map, fwd_plan, scratch)) {
-    Schedule sc = schedule((hipStream_t)stream, ks, false);
-    rc = split_backward(p, rank_map, fwd_plan, scratch, sc);
+  if (split_ok(c)) {
+    Schedule sc = schedule(st, ks, Chains::never);
+    rc = split_backward(c, p, sc);
   } else {
-    if (p.gfix) rc = launch_grad_fix_bound(p, (hipStream_t)stream);
-    if (!rc) rc = launch_bwd(p, (hipStream_t)stream);
+    if (p.gfix) rc = launch_grad_fix_bound(p, st);
+    if (!rc) rc = launch_bwd(p, st);
   }
-  return rc ? rc : det_end(p, (hipStream_t)stream);
+  return rc ? rc : det_end(c, p, st);
 }
 
 size_t ssg_grad_fix_bytes(int B, int C, int H, int W) { return grad_fix_bytes(B, C, H, W); }
 
-static size_t partials_bytes(int B, int H, int W, int n_rows) {
-  return align_up(2 * sizeof(float) * bwd_max_partials(B, H, W, n_rows) + 64, 256);
-}
-
 size_t ssg_loss_scratch_bytes(int B, int H, int W, int n_rows, int ks) {
-  return partials_bytes(B, H, W, n_rows) + split_scratch_bytes(n_rows, ks);
+  return carve_backward_scratch(B, H, W, n_rows, ks, GRAD_LOSS).end;
 }
 
-static int loss_backward(const float *sr, int B, int C, int H, int W, const int *edges, const int *tile_order,
-                         const int *rank_map, const int *fwd_plan, const int *n_edges_dev, int n_rows, int ks, int kw,
-                         float sigma, int generalization, float *ssg_sr, float *ssg_gt, float w_l1, float w_kl,
-                         const float *upstream, float *loss_out, float *grad_sr, void *scratch, void *grad_fix,
-                         const double *row_scale, bool rows_scratch, bool fix_zeroed, bool grad_is_output,
-                         Schedule &sc, const TileMajor *tm = nullptr, bool nan_on_overflow = false) {
-  if (n_rows < 0 || !sizes_ok(ks, kw) || B <= 0 || C <= 0 || !loss_out) return SSG_E_BADARG;
-  if (H <= ks / 2 || W <= ks / 2) return SSG_E_IMAGESMALL;
+static int loss_backward(const Call &c, Schedule &sc) {
   const hipStream_t st = sc.st;
-  if (n_rows == 0) return (int)hipMemsetAsync(loss_out, 0, 2 * sizeof(float), st);
-  if (!sr || !edges || !ssg_sr || !ssg_gt || !scratch) return SSG_E_BADARG;
-  BwdParams p{};
-  p.img = sr;
-  p.grad = grad_sr;
-  p.edges = edges;
-  p.estride = 3;
-  p.n_dev = n_edges_dev;
-  p.n_host = n_rows;
-  p.B = B;
-  p.C = C;
-  p.H = H;
-  p.W = W;
-  p.order = tile_order;
-  p.mode = GRAD_LOSS;
-  p.ssg = ssg_sr;
-  p.ssg2 = ssg_gt;
-  p.sigma = sigma;
-  p.generalization = generalization;
-  p.w_l1 = w_l1;
-  p.w_kl = w_kl;
-  p.partials = (float *)scratch;
-  p.upstream = upstream;
-  p.ks = ks;
-  p.kw = kw;
-  p.dbg = (dbg_mask() >> 8) & 0xff;
-  p.row_scale = row_scale;
-  p.rows_scratch = rows_scratch ? 1 : 0;
-  const bool split = split_ok(ks, kw, C, rank_map, fwd_plan, scratch);
-  if (row_scale && !split) return SSG_E_BADARG;  // only ssg_grad_rows rescales
-  int rc = det_begin(p, grad_fix, st, fix_zeroed);
+  int rc = 0;
+  if (call_ends(c, LOSS_BACKWARD, st, rc)) return rc;
+  BwdParams p = bwd_params(c, GRAD_LOSS);
+  const bool split = split_ok(c);
+  if (c.row_scale && !split) return SSG_E_BADARG;  // only ssg_grad_rows rescales
+  rc = det_begin(c, p, st);
   if (rc) return rc;
   // criteria sums: the backward kernel's workgroups, or ssg_grad_rows' -- per-class row passes: two sets of
   // grow_grid(n_rows) slots -- and ssg_rows_tm's
   // (ssg_grad_rows' slots come in sets of grow_grid(n_rows), live up to the device's row count: LossFinalize::set_size)
-  const int n_tm = split ? split_tm_tiles(p, tm) : 0;
+  const int n_tm = split ? split_tm_tiles(p, c.tm) : 0;
   const int nparts = !split ? (int)bwd_grid(p)
-                            : (split_row_classes(p, n_tm) ? 2 : 1) * (int)grow_grid(n_rows) + rows_tm_parts(n_tm);
-  const int set_size = split && n_tm == 0 ? (int)grow_grid(n_rows) : 0;
-  const LossFinalize fin{p.partials, nparts, n_edges_dev, n_rows, ks * ks, w_l1, w_kl, loss_out, nan_on_overflow ? 1 : 0, set_size};
+                            : (split_row_classes(p, n_tm) ? 2 : 1) * (int)grow_grid(c.n_rows) + rows_tm_parts(n_tm);
+  const int set_size = split && n_tm == 0 ? (int)grow_grid(c.n_rows) : 0;
+  const LossFinalize fin{p.partials, nparts, c.n_dev, c.n_rows, c.ks * c.ks, c.w_l1, c.w_kl, c.loss_out, c.nan_on_overflow ? 1 : 0, set_size};
   bool fin_done = false;
   if (split) {
-    rc = split_backward(p, rank_map, fwd_plan, (char *)scratch + partials_bytes(B, H, W, n_rows), sc, &fin, &fin_done, tm);
+    rc = split_backward(c, p, sc, &fin, &fin_done);
   } else {
     p.fix_inline = p.gfix ? 1 : 0;   // (GRAD_LOSS: the backward kernel derives the a-priori scale itself -- one launch less)
     rc = launch_bwd(p, st);
@@ -993,8 +1142,8 @@ static int loss_backward(const float *sr, int B, int C, int H, int W, const int 
   // (the finalize rides in the flush's last workgroup when its partial sums are few -- 256 threads play its 1,024 lanes: C5's
   // 70 k partials took 30 us there against 10 + 11 as two launches)
   // (sets of slots are read up to the device's row count only: what counts is their live prefix, bounded by the host's)
-  const int fin_reads = set_size > 0 ? (nparts / set_size) * ((n_rows + 3) / 4) : nparts;
-  if (!rc) rc = det_end(p, st, grad_is_output, (fin_done || fin_reads > 8192) ? nullptr : &fin, &fin_done);
+  const int fin_reads = set_size > 0 ? (nparts / set_size) * ((c.n_rows + 3) / 4) : nparts;
+  if (!rc) rc = det_end(c, p, st, (fin_done || fin_reads > 8192) ? nullptr : &fin, &fin_done);
   if (rc || fin_done) return rc;
   return launch_loss_finalize(fin, st);
 }
@@ -1005,16 +1154,39 @@ int ssg_loss_backward(const float *sr, int B, int C, int H, int W, const int *ed
                       float *ssg_sr, float *ssg_gt, float w_l1, float w_kl, const float *upstream,
                       float *loss_out, float *grad_sr, void *scratch, void *grad_fix, const double *row_scale,
                       int rows_are_scratch, ssg_stream_t stream) {
-  Schedule sc = schedule((hipStream_t)stream, ks, true);
-  const int rc = loss_backward(sr, B, C, H, W, edges, tile_order, rank_map, fwd_plan, n_edges_dev, n_rows, ks, kw, sigma,
-                               generalization, ssg_sr, ssg_gt, w_l1, w_kl, upstream, loss_out, grad_sr, scratch,
-                               grad_fix, row_scale, rows_are_scratch != 0, false, false, sc);
+  Call c;
+  c.img = sr;
+  c.B = B;
+  c.C = C;
+  c.H = H;
+  c.W = W;
+  c.edges = edges;
+  c.order = tile_order;
+  c.rank = rank_map;
+  c.plan = fwd_plan;
+  c.n_dev = n_edges_dev;
+  c.n_rows = n_rows;
+  c.ks = ks;
+  c.kw = kw;
+  c.sigma = sigma;
+  c.generalization = generalization;
+  c.ssg = ssg_sr;
+  c.ssg2 = ssg_gt;
+  c.w_l1 = w_l1;
+  c.w_kl = w_kl;
+  c.upstream = upstream;
+  c.loss_out = loss_out;
+  c.grad = grad_sr;
+  c.scratch = scratch;
+  c.grad_fix = grad_fix;
+  c.row_scale = const_cast<double *>(row_scale);   // (a backward only reads the row scales)
+  c.rows_scratch = rows_are_scratch != 0;
+  Schedule sc = schedule((hipStream_t)stream, ks, Chains::possible);
+  const int rc = loss_backward(c, sc);
   const int rcj = join_side(sc);   // (an error between the row passes' fork and the backward's join leaves it open)
   return rc ? rc : rcj;
 }
 
-// a capacity as the sizes below count it: room for one row at least
-static size_t rows_of(int capacity) { return (size_t)(capacity > 0 ? capacity : 1); }
 // two row-major regions (sr, gt); at k_s = 49 two tile-major regions of the same size behind them
 static size_t rows_region_bytes(int capacity, int ks) { return align_up(sizeof(float) * rows_of(capacity) * ks * ks, 256); }
 // (a tile-major region: capacity / 128 slots and a spare one for the short strips of ssg_fwd_strip)
@@ -1073,11 +1245,13 @@ int ssg_loss_workspace_layout(int B, int H, int W, int capacity, int ks, int fus
   return 0;
 }
 
+// ssg_loss_fwd_bwd adds into the caller's gradient, ssg_loss_step writes it
+enum class GradientIs { accumulated, output };
 static int loss_fwd_bwd_impl(const float *sr, const float *gt, const void *mask, int mask_kind, int mask_channels, int B,
                              int C, int H, int W, int ks, int kw, float sigma, float eps, int generalization, float w_l1,
                              float w_kl, int mask_stride, float lap_threshold, int capacity, float *ssg_sr,
                              float *ssg_gt, int *counts, float *loss_out, float *grad_sr, void *workspace,
-                             size_t workspace_bytes, void *grad_fix, bool grad_is_output, ssg_stream_t stream) {
+                             size_t workspace_bytes, void *grad_fix, GradientIs gradient, ssg_stream_t stream) {
   if (!sr || !gt || !counts || !loss_out || !workspace || capacity <= 0) return SSG_E_BADARG;
   if ((ssg_sr == nullptr) != (ssg_gt == nullptr)) return SSG_E_BADARG;
   if (mask_kind != 2 && !mask) return SSG_E_BADARG;
@@ -1089,12 +1263,38 @@ static int loss_fwd_bwd_impl(const float *sr, const float *gt, const void *mask,
   // the edge-list builder's first kernel clears the row scales, the fixed-point sums and (ssg_loss_step) the gradient
   // with 16-byte stores: offset views of a larger buffer must keep that alignment (include/ssg_hip.h)
   if ((((uintptr_t)workspace) | ((uintptr_t)grad_fix) | ((uintptr_t)grad_sr)) & 15) return SSG_E_ALIGN;
+  const hipStream_t st = (hipStream_t)stream;
+  const bool grad_is_output = gradient == GradientIs::output;
   char *ws = (char *)workspace;
-  TileMajor tm;
-  if (fused) {
-    ssg_sr = (float *)(ws + lw.rows[0]);
-    ssg_gt = (float *)(ws + lw.rows[1]);
-  }
+  int *edges = (int *)(ws + lw.edges);
+  int *rank = (int *)(ws + lw.rank);
+  Call c;
+  c.img = sr;
+  c.img2 = gt;
+  c.B = B;
+  c.C = C;
+  c.H = H;
+  c.W = W;
+  c.edges = edges;
+  c.rank = rank;
+  c.n_dev = counts;
+  c.n_rows = capacity;
+  c.ks = ks;
+  c.kw = kw;
+  c.sigma = sigma;
+  c.eps = eps;
+  c.generalization = generalization;
+  c.w_l1 = w_l1;
+  c.w_kl = w_kl;
+  c.ssg = fused ? (float *)(ws + lw.rows[0]) : ssg_sr;
+  c.ssg2 = fused ? (float *)(ws + lw.rows[1]) : ssg_gt;
+  c.loss_out = loss_out;
+  c.grad = grad_sr;
+  c.grad_fix = grad_fix;
+  c.scratch = ws + lw.lscratch;
+  c.rows_scratch = fused;
+  c.grad_is_output = grad_is_output;
+  c.nan_on_overflow = true;
   // tile-major rows: always in the fused step; in a materialising call when the caller's workspace has room for the
   // two regions (ssg_loss_tm_bytes) -- ssg_rows_tm_mat then writes the normalised SSG rows from them
   // (ssg_fwd_strip addresses a region with 32-bit ELEMENT offsets: regions of 2^32 floats = 16 GB and more -- from 1.78 M
@@ -1102,86 +1302,61 @@ static int loss_fwd_bwd_impl(const float *sr, const float *gt, const void *mask,
   if (ks == 49 && kw == 13 && C == 3 && generalization && tile_major_enabled() &&
       (size_t)(lw.tm_slots + 1) * (size_t)(ks * ks) * TM_PX < (1ull << 32) &&
       (fused || workspace_bytes >= base_bytes + ssg_loss_tm_bytes(capacity, ks))) {
-    tm.rows[0] = (float *)(ws + lw.tm[0]);
-    tm.rows[1] = (float *)(ws + lw.tm[1]);
-    tm.slots = lw.tm_slots;
+    c.tm.rows[0] = (float *)(ws + lw.tm[0]);
+    c.tm.rows[1] = (float *)(ws + lw.tm[1]);
+    c.tm.slots = lw.tm_slots;
   }
-  int *edges = (int *)(ws + lw.edges);
-  int *rank = (int *)(ws + lw.rank);
+  // the mask of the call (kind 2: the Laplacian of gt's three channels), the gradient's bytes and whether the
+  // deterministic sums are in use: the tiny path and the general path both take them from here
+  const void *mask_src = mask_kind == 2 ? (const void *)gt : mask;
+  const int mask_ch = mask_kind == 2 ? 3 : mask_channels;
+  const size_t grad_bytes = sizeof(float) * (size_t)B * C * H * W, fix_bytes = grad_fix_bytes(B, C, H, W);
+  // the fixed-point gradient sums start at zero: cleared by the edge-list builder's first kernel
+  const bool zero_fix = grad_fix && grad_sr;
+  // a gradient that is an OUTPUT: the deterministic flush assigns it; with fp32 atomics it is cleared by the builder's
+  // first kernel (whole 16-byte granules; a tail of < 16 bytes by the memset below)
+  void *const zero_grad = (grad_is_output && grad_sr && !zero_fix) ? (void *)grad_sr : nullptr;
+  c.fix_zeroed = zero_fix;
   // small (11,5) steps: one workgroup builds the edge list, one workgroup per edge pixel does the rest (ssg_tiny.hip)
   if (g_tiny_step.load(std::memory_order_relaxed) && tiny_step_supported(ks, kw, C, capacity) && tiny_edge_list_ok(B, H, W) &&
       B > 0 && H > ks / 2 && W > ks / 2 && mask_kind >= 0 && mask_kind <= 2 && (mask_kind == 2 || mask_channels > 0)) {
-    const bool fixed = grad_fix && grad_sr;
     int *ticket = (int *)(ws + lw.escratch);
-    int rc = launch_tiny_edge_list(mask_kind == 2 ? (const void *)gt : mask, mask_kind, mask_kind == 2 ? 3 : mask_channels, B, H, W,
-                                   mask_stride, lap_threshold, edges, capacity, counts, rank, ticket, 16,
-                                   fixed ? grad_fix : nullptr, grad_fix_bytes(B, C, H, W),
-                                   (grad_is_output && grad_sr && !fixed) ? (void *)grad_sr : nullptr,
-                                   sizeof(float) * (size_t)B * C * H * W, (hipStream_t)stream);
+    const int rc = launch_tiny_edge_list(mask_src, mask_kind, mask_ch, B, H, W, mask_stride, lap_threshold, edges, capacity, counts,
+                                         rank, ticket, 16, zero_fix ? grad_fix : nullptr, fix_bytes, zero_grad, grad_bytes, st);
     if (rc) return rc;
-    TinyParams t{};
-    t.img[0] = sr;
-    t.img[1] = gt;
-    t.out[0] = fused ? nullptr : ssg_sr;
-    t.out[1] = fused ? nullptr : ssg_gt;
-    t.edges = edges;
-    t.n_dev = counts;
-    t.n_host = capacity;
-    t.B = B;
-    t.H = H;
-    t.W = W;
-    t.sigma = sigma;
-    t.eps = eps;
-    t.generalization = generalization;
-    t.w_l1 = w_l1;
-    t.w_kl = w_kl;
-    t.grad = grad_sr;
-    t.gfix = fixed ? (long long *)grad_fix : nullptr;
-    t.assign = grad_is_output ? 1 : 0;
-    t.partials = (float *)(ws + lw.lscratch);
-    t.loss_out = loss_out;
-    t.ticket = ticket;
-    t.nan_on_overflow = 1;
-    t.dbg = env_int("SSG_TINY_DBG", 0);
-    return launch_tiny_step(t, C, (hipStream_t)stream);
+    return launch_tiny_step(tiny_params(c, ticket), C, st);
   }
   int *order = (int *)(ws + lw.order);
   int *plan = (int *)(ws + lw.plan);
   void *escratch = ws + lw.escratch;
-  void *lscratch = ws + lw.lscratch;
   double *row_scale = (double *)(ws + lw.row_scale);
+  c.plan = plan;
   // (deferred normalisation wherever the split backward -- whose ssg_grad_rows pass rescales -- follows)
-  const bool defer = split_ok(ks, kw, C, rank, plan, lscratch) && dense_supported(ks, kw, C);
-  if (!defer) tm.slots = 0;
+  const bool defer = split_ok(c) && dense_supported(ks, kw, C);
+  if (!defer) c.tm.slots = 0;
   // with the plan in use every kernel takes its job order from it: the full tile-major order is not built (3 launches)
   if (defer) order = nullptr;
   // kernel sizes without shared-term kernels ((11,5), other channel counts) have no use for a plan: not built
   // (4 launches of 4-5 us each: BASELINE's C1 step is 14 dependent launches long)
   if (!dense_supported(ks, kw, C)) plan = nullptr;
-  // the row scales and the fixed-point gradient sums start at zero: cleared by the edge-list builder's first kernel
+  c.order = order;
+  c.plan = plan;
+  // the row scales start at zero like the fixed-point sums: cleared by the edge-list builder's first kernel
   // (16-byte granules: both sizes are multiples of 16)
-  const bool zero_fix = grad_fix && grad_sr;
+  c.row_scale = defer ? row_scale : nullptr;
+  c.row_scale_zeroed = defer;
   // the schedule of the whole step, from the hint the builder below has not overwritten yet: two chains where there is a
   // gradient and the sizes have a dense / direct split
-  Schedule sc = schedule((hipStream_t)stream, ks, defer && grad_sr);
-  const size_t fix_bytes = grad_fix_bytes(B, C, H, W), rs_bytes = 2 * sizeof(double) * (size_t)capacity;
-  int rc = edge_list_impl(mask_kind == 2 ? (const void *)gt : mask, mask_kind, mask_kind == 2 ? 3 : mask_channels, B, H,
-                          W, mask_stride, lap_threshold, ks, edges, capacity, counts, rank, order, plan, escratch,
-                          defer ? (void *)row_scale : nullptr, rs_bytes, zero_fix ? grad_fix : nullptr, fix_bytes,
-                          // a gradient that is an OUTPUT: the deterministic flush assigns it; with fp32 atomics it is
-                          // cleared here (whole 16-byte granules; a tail of < 16 bytes by the memset below)
-                          (grad_is_output && grad_sr && !zero_fix) ? (void *)grad_sr : nullptr,
-                          sizeof(float) * (size_t)B * C * H * W, stream);
-  if (!rc && grad_is_output && grad_sr && !zero_fix && ((sizeof(float) * (size_t)B * C * H * W) & 15))
-    rc = (int)hipMemsetAsync((char *)grad_sr + ((sizeof(float) * (size_t)B * C * H * W) & ~(size_t)15), 0,
-                             (sizeof(float) * (size_t)B * C * H * W) & 15, (hipStream_t)stream);
+  Schedule sc = schedule(st, ks, defer && grad_sr ? Chains::possible : Chains::never);
+  const size_t rs_bytes = 2 * sizeof(double) * (size_t)capacity;
+  int rc = edge_list_impl(mask_src, mask_kind, mask_ch, B, H, W, mask_stride, lap_threshold, ks, edges, capacity, counts, rank,
+                          order, plan, escratch, c.row_scale, rs_bytes, zero_fix ? grad_fix : nullptr, fix_bytes, zero_grad,
+                          grad_bytes, stream);
+  if (!rc && zero_grad && (grad_bytes & 15))
+    rc = (int)hipMemsetAsync((char *)grad_sr + (grad_bytes & ~(size_t)15), 0, grad_bytes & 15, st);
   if (rc) return rc;
-  rc = map_forward_impl(sr, gt, B, C, H, W, edges, order, rank, plan, counts, capacity, ks, kw, sigma, eps,
-                        generalization, ssg_sr, ssg_gt, defer ? row_scale : nullptr, defer, sc, &tm);
-  if (!rc)
-    rc = loss_backward(sr, B, C, H, W, edges, order, rank, plan, counts, capacity, ks, kw, sigma, generalization,
-                       ssg_sr, ssg_gt, w_l1, w_kl, nullptr, loss_out, grad_sr, lscratch, grad_fix,
-                       defer ? row_scale : nullptr, fused, zero_fix, grad_is_output && zero_fix, sc, &tm, true);
+  rc = map_forward_impl(c, sc);
+  if (!rc) rc = loss_backward(c, sc);
   const int rcj = join_side(sc);   // (an error between the forward's fork and the backward's join leaves it open)
   return rc ? rc : rcj;
 }
@@ -1193,7 +1368,7 @@ int ssg_loss_fwd_bwd(const float *sr, const float *gt, const void *mask, int mas
                      void *grad_fix, ssg_stream_t stream) {
   return loss_fwd_bwd_impl(sr, gt, mask, mask_kind, mask_channels, B, C, H, W, ks, kw, sigma, eps, generalization, w_l1,
                            w_kl, mask_stride, lap_threshold, capacity, ssg_sr, ssg_gt, counts, loss_out, grad_sr,
-                           workspace, workspace_bytes, grad_fix, false, stream);
+                           workspace, workspace_bytes, grad_fix, GradientIs::accumulated, stream);
 }
 
 int ssg_loss_step(const float *sr, const float *gt, const void *mask, int mask_kind, int mask_channels, int B, int C,
@@ -1203,7 +1378,7 @@ int ssg_loss_step(const float *sr, const float *gt, const void *mask, int mask_k
                   ssg_stream_t stream) {
   return loss_fwd_bwd_impl(sr, gt, mask, mask_kind, mask_channels, B, C, H, W, ks, kw, sigma, eps, generalization, w_l1,
                            w_kl, mask_stride, lap_threshold, capacity, ssg_sr, ssg_gt, counts, loss_out, grad_sr,
-                           workspace, workspace_bytes, grad_fix, true, stream);
+                           workspace, workspace_bytes, grad_fix, GradientIs::output, stream);
 }
 
 int ssg_augment_crop(const void *src, void *dst, int elem_bytes, int B, int C, int Hs, int Ws, int Ho, int Wo,
