@@ -66,6 +66,7 @@ typedef void *ssg_stream_t; /* hipStream_t */
 /* 6, additive: + ssg_bbl_workspace_bytes, ssg_bbl_search, ssg_bbl_loss, ssg_flat_mask (BebyGAN's best-buddy loss and
  * flat mask, section (G)); again nothing existing changed. */
 /* 6, additive: + ssg_synth_kernels and its record (the degradation chain's blur and sinc kernels, section (I)). */
+/* 6, additive: + ssg_resample, ssg_resample_table / _ksize / _tile / _max_ratio (Pillow's 8-bit resize, section (N)). */
 int ssg_abi_version(void);
 const char *ssg_status_string(int status);
 /* Device-side refusals that no return value can carry (everything is asynchronous): waits for `stream`, then returns
@@ -753,6 +754,52 @@ int ssg_ssim_taps(int window_size, float *taps_out);
 int ssg_ssim_loss(const float *x, const float *y, int B, int C, int H, int W, int window_size,
                   float *grad_x /* nullable */, double *sums_out, void *workspace, size_t workspace_bytes,
                   ssg_stream_t stream);
+
+/* ---------------------------------------------------------------- (N) ----
+ * Pillow's 8-bit convolution resize (PIL.Image.resize(size, resample) with box=None, reducing_gap=None: libImaging's
+ * ImagingResample) -- the LANCZOS resize of the Diffusion fork's load_img (test.py:111-120) and of the multiscale
+ * preparation scripts (generate_multiscale_img.py, generate_multiscale_DF2K.py), ssl_amd/csrc/ssg_resample.hip.  The
+ * algorithm is integer from its coefficient tables on, so the bytes are Pillow's: no tolerance.
+ * For one axis with input size `in` and output size `out`, S = 3 (LANCZOS), 2 (BICUBIC), 1 (BILINEAR, HAMMING), 0.5 (BOX):
+ *   scale = in / out, fs = max(scale, 1), support = S fs, ksize = 2 ceil(support) + 1; for every output index xx
+ *   center = (xx + 0.5) scale, xmin = max((int)(center - support + 0.5), 0), n = min((int)(center + support + 0.5), in)
+ *   - xmin, w_i = f((i + xmin - center + 0.5) (1 / fs)), ww their sum in index order, w_i /= ww when ww != 0, all fp64;
+ *   k_i = (int)(w_i 2^22 + 0.5) for w_i >= 0, (int)(w_i 2^22 - 0.5) otherwise (C truncation); zeros from n to ksize.
+ *   A pass is clip8((2^21 + sum_i px[xmin + i] k_i) >> 22) on an int32 accumulator.  The columns are filtered first, into
+ *   bytes; the rows are filtered from those bytes.  A pass whose axis keeps its size is not run; bands are independent.
+ * ssg_resample_ksize, ssg_resample_table: HOST functions, no device: the tables above, with the C library's sin and cos
+ *   (computing them on the device could move a coefficient by one).  bounds[out][2] = {xmin, n}, coef[out][ksize].
+ *   ksize < 0 is a status (SSG_E_BADARG for in, out < 1 or an unknown filter).
+ * ssg_resample: src uint8 (B,Hin,Win,C) contiguous on the device, C 1 or 3; the four tables int32 on the device, those of
+ *   an axis that keeps its size are not read and may be NULL.  One launch: a workgroup of 256 threads per output tile
+ *   reads the tile's input footprint into LDS, filters its columns into a byte intermediate in LDS and the rows from
+ *   that.  No atomics: image b of a batch gets the bytes it gets alone.  No allocation, synchronisation or host read.
+ *   out_kind  SSG_RESAMPLE_U8_HWC the byte v, uint8 (B,Hout,Wout,C); SSG_RESAMPLE_F32_UNIT (float)v / 255.0f, fp32
+ *             (B,C,Hout,Wout) (what ssg_edge_mask_laplacian takes); SSG_RESAMPLE_F32_SIGNED 2.0f ((float)v / 255.0f) -
+ *             1.0f, fp32 (B,C,Hout,Wout): load_img's numpy / torch expression bit for bit.
+ *   The tile is chosen per call from a short list (32 x 64, 16 x 64, 16 x 32, 8 x 32): the first whose footprint,
+ *   intermediate and coefficient rows take at most 20 KiB of LDS (eight workgroups per CU), else the one that takes the
+ *   least, which must fit the 160 KiB of a CU.  The fused kernel takes every ratio in / out <= 8 per axis for all five
+ *   filters (114,176 B at most); beyond that ssg_resample returns SSG_E_TOOLARGE (resize in two steps, or on the CPU).
+ * Status, decided before the launch with the output untouched: SSG_E_BADARG for a null src or out, out == src, a null
+ * table of an axis that changes size, C not 1 or 3, B or a size < 1, an unknown filter or out_kind; SSG_E_TOOLARGE for
+ * more than 2^31 - 1 input or output elements, or in > 8 out on an axis.
+ * ssg_resample_tile: the first tile of the list (rows, columns); every other tile divides it.
+ * ssg_resample_max_ratio: 8. */
+#define SSG_RESAMPLE_LANCZOS 1   /* Pillow's Image.Resampling numbers */
+#define SSG_RESAMPLE_BILINEAR 2
+#define SSG_RESAMPLE_BICUBIC 3
+#define SSG_RESAMPLE_BOX 4
+#define SSG_RESAMPLE_HAMMING 5
+#define SSG_RESAMPLE_U8_HWC 0
+#define SSG_RESAMPLE_F32_UNIT 1
+#define SSG_RESAMPLE_F32_SIGNED 2
+int ssg_resample_ksize(int in, int out, int filter);
+int ssg_resample_table(int in, int out, int filter, int *bounds, int *coef);
+int ssg_resample_tile(int *tile_rows, int *tile_cols);
+int ssg_resample_max_ratio(void);
+int ssg_resample(const uint8_t *src, int B, int C, int Hin, int Win, int Hout, int Wout, int filter, const int *xbounds,
+                 const int *xcoef, const int *ybounds, const int *ycoef, int out_kind, void *out, ssg_stream_t stream);
 
 #ifdef SSG_PROFILE
 /* PROFILING BUILD ONLY (libssg_hip_prof.so, compiled with -DSSG_PROFILE; the product library libssg_hip.so does not

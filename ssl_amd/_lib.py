@@ -95,6 +95,11 @@ PROTOTYPES = {
     "ssg_ssim_grid_cap": (_i, []),
     "ssg_ssim_taps": (_i, [_i, _vp]),
     "ssg_ssim_loss": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
+    "ssg_resample_ksize": (_i, [_i, _i, _i]),
+    "ssg_resample_table": (_i, [_i, _i, _i, _vp, _vp]),
+    "ssg_resample_tile": (_i, [_vp, _vp]),
+    "ssg_resample_max_ratio": (_i, []),
+    "ssg_resample": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp]),
     # include/similarity.h: the reference operator's own (void, stream-less) interface
     "ssg_ref_compute_similarity": (None, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i]),
     "ssg_ref_compute_similarity_backward": (None, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i]),

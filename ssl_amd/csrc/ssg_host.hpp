@@ -120,6 +120,15 @@ size_t ssim_workspace_bytes(int B, int C, int H, int W);
 int launch_ssim_loss(const float *x, const float *y, int B, int C, int H, int W, int window_size, float *grad_x,
                      double *sums_out, void *workspace, size_t workspace_bytes, hipStream_t st);
 
+// ---- ssg_resample.hip: Pillow's 8-bit convolution resize (entry points beside its kernel) ----
+int resample_ksize(int in, int out, int filter);                                   // host only
+int resample_table(int in, int out, int filter, int *bounds, int *coef);           // host only: fp64, libm's sin / cos
+void resample_tile_shape(int *th, int *tw);
+int resample_max_ratio();
+int launch_resample(const uint8_t *src, int B, int C, int Hin, int Win, int Hout, int Wout, int filter,
+                    const int *xbounds, const int *xcoef, const int *ybounds, const int *ycoef, int out_kind, void *out,
+                    hipStream_t st);
+
 // ---- ssg_api.hip ----
 // host-mapped {rows for the direct kernels, dense tiles} of the device's last plan, written by the edge-list builder's
 // scan kernel (nullptr: no hint wanted, or none allocated yet and `st` is being captured)
