@@ -206,6 +206,82 @@ def fit(feat, mu_pris, cov_pris):
     return dict(score=math.sqrt(q2), q2=q2, cond=float(ev[-1] / ev[0]), ratio=float(ev[0] / ev[-1]), sigma=sigma, d=d)
 
 
+def fit_by_numpy(feat, mu_pris, cov_pris):
+    """q^2 once more by the library calls the metric is defined with: np.nanmean of the columns, np.cov of the rows
+    without a NaN, np.linalg.pinv.  Another order of every sum than fit's, and an SVD instead of an LU solve."""
+    feat = np.asarray(feat, np.float64)
+    mu = np.nanmean(feat, axis=0)
+    cov = np.cov(feat[~np.isnan(feat).any(axis=1)], rowvar=False)
+    d = np.asarray(mu_pris, np.float64).reshape(1, -1) - mu.reshape(1, -1)
+    return float((d @ np.linalg.pinv((np.asarray(cov_pris, np.float64) + cov) / 2) @ d.T)[0, 0])
+
+
+# ----------------------------------------------------------------------------------------------- the comparisons ---
+# What tests/test_gpu_niqe_blocks.py holds the kernels to, as functions of arrays, so that tests/test_cpu_niqe_blocks.py
+# can show that they refuse wrong outputs.  Each returns the measured share of its bound and raises AssertionError.
+ALPHA = [c + 18 * s for s in (0, 1) for c in ALPHA_COLUMNS]
+OTHER = [c for c in range(NF) if c not in ALPHA]
+PLANE2_BOUND = 255 * 2.0 ** -44            # derived in test_gpu_niqe.test_planes
+FEATURE_BOUND = 1e-10
+
+
+def score_bound(rfit):
+    """|q2 - q2_restatement| may reach 64 cond(Sigma) 2.2e-16 q2 (absolute).
+
+    Where the 64 comes from: q2 = d' Sigma^-1 d moves by at most cond(Sigma) |dSigma| / |Sigma| (to first order, plus
+    twice the relative error of d, which the factor cond dwarfs) when Sigma is perturbed.  Two correct fp64 fits differ
+    in Sigma by the rounding of their sums and of their solves: a 36 x 36 factorisation and substitution has a backward
+    error of about 36 u in the worst case, and a sum of n products in some order errs by n u in the worst case and by
+    sqrt(n) u typically.  64 u allows the solve's 36 u and 28 u for the sums: a worst-case allowance up to 28 rows, a
+    typical-case one (sqrt(n) <= 28) up to 784 rows, which covers the 294 rows of a 2040 x 1356 image.  It has no
+    row-count term, and needs none at the sizes tested: two orders of summation (fit against fit_by_numpy) use 1.4e-5 of
+    it at 258 rows and 3.3e-6 at 8 (tests/test_cpu_niqe_blocks.py asserts less than 1 % and prints the shares), because
+    the factor cond(Sigma) is reached only by a d along Sigma's smallest eigenvector, which no image's d is."""
+    return 64 * rfit["cond"] * 2.2e-16 * rfit["q2"]
+
+
+def compare_planes(p1, p2, want_p1):
+    """Plane 1 (float32) bit-equal to want_p1; plane 2 within PLANE2_BOUND of the restatement on plane 1."""
+    want_p1 = np.asarray(want_p1)
+    assert p1.dtype == np.float32 and p1.shape == want_p1.shape, (p1.dtype, p1.shape, want_p1.shape)
+    assert np.array_equal(p1.view(np.uint32), want_p1.astype(np.float32).view(np.uint32)), "plane 1"
+    want_p2 = plane2(p1.astype(np.float64))
+    assert p2.dtype == np.float64 and p2.shape == want_p2.shape, (p2.dtype, p2.shape, want_p2.shape)
+    dev = float(np.abs(p2 - want_p2).max())
+    assert dev <= PLANE2_BOUND, ("plane 2", dev)
+    return dev / PLANE2_BOUND
+
+
+def compare_features(got, want, t):
+    """got against the restatement's rows `want` with their fits' rhatnorm `t`: the NaN pattern and every alpha equal
+    (which rests on no t lying within 1e-9 of a midpoint: asserted), the rest within FEATURE_BOUND relative."""
+    got, want = np.asarray(got), np.asarray(want)
+    assert got.shape == want.shape and got.dtype == np.float64, (got.shape, want.shape, got.dtype)
+    differ = np.argwhere(np.isnan(got) != np.isnan(want))
+    assert differ.size == 0, ("NaN pattern at (row, column)", differ[:8].tolist())
+    assert midpoint_margin(t).min() > 1e-9, "a fit within 1e-9 of a midpoint"
+    differ = np.argwhere(got[:, ALPHA] != want[:, ALPHA])
+    assert differ.size == 0, ("alpha at (row, fit)", differ[:8].tolist())
+    a, b = got[:, OTHER], want[:, OTHER]
+    ok = ~np.isnan(b)
+    if not ok.any():
+        return 0.0
+    rel = float((np.abs(a - b)[ok] / np.abs(b[ok])).max())
+    assert rel <= FEATURE_BOUND, ("features", rel)
+    return rel / FEATURE_BOUND
+
+
+def compare_score(score, rfit):
+    """A score against the restatement's fit: both NaN, or q2 within score_bound."""
+    if np.isnan(rfit["score"]):
+        assert np.isnan(score), ("a score where the restatement has none", score)
+        return 0.0
+    assert np.isfinite(score), score
+    dev, bound = abs(score * score - rfit["q2"]), score_bound(rfit)
+    assert dev <= bound, ("score", score, rfit["score"], dev / bound)
+    return dev / bound
+
+
 def niqe(img, crop_border, mu_pris, cov_pris, input_order='HWC', convert_to='y'):
     p1 = plane1(img, crop_border, input_order, convert_to)
     p2 = plane2(p1)

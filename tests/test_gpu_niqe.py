@@ -3,7 +3,9 @@ reference's recorded planes (golden/f26_niqe.npz): the two planes, the 36 featur
 reproducibility, the four input kinds, 'gray', the refusal of an image without a block, and the Python layer.
 
 No grid of these kernels is capped (one thread per pixel, one workgroup per tile / per block and scale / per image), so
-there is no second trip to cross.  Every case runs once (module cache); the tests share the results."""
+no grid-stride loop has a second trip to cross.  niqe_fit's loops over the ROWS do (the flags past one workgroup's
+threads, the seven row lanes of the column means), and the fixture's six blocks at most reach none of them:
+test_gpu_niqe_blocks.py does, on generated inputs.  Every case runs once (module cache); the tests share the results."""
 import numpy as np
 import pytest
 import torch
