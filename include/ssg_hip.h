@@ -67,6 +67,7 @@ typedef void *ssg_stream_t; /* hipStream_t */
  * flat mask, section (G)); again nothing existing changed. */
 /* 6, additive: + ssg_synth_kernels and its record (the degradation chain's blur and sinc kernels, section (I)). */
 /* 6, additive: + ssg_resample, ssg_resample_table / _ksize / _tile / _max_ratio (Pillow's 8-bit resize, section (N)). */
+/* 6, additive: + ssg_imresize, ssg_imresize_out_size / _taps / _table / _tiles (MATLAB's bicubic imresize, section (O)). */
 int ssg_abi_version(void);
 const char *ssg_status_string(int status);
 /* Device-side refusals that no return value can carry (everything is asynchronous): waits for `stream`, then returns
@@ -800,6 +801,54 @@ int ssg_resample_tile(int *tile_rows, int *tile_cols);
 int ssg_resample_max_ratio(void);
 int ssg_resample(const uint8_t *src, int B, int C, int Hin, int Win, int Hout, int Wout, int filter, const int *xbounds,
                  const int *xcoef, const int *ybounds, const int *ycoef, int out_kind, void *out, ssg_stream_t stream);
+
+/* ---------------------------------------------------------------- (O) ----
+ * MATLAB's bicubic imresize as the reference's Python restates it (basicsr/utils/matlab_functions.py:imresize, KAIR's
+ * utils_image.py:imresize / imresize_np; generate_bicubic_img.m calls the original), ssl_amd/csrc/ssg_imresize.hip: any
+ * scale > 0 (the same on both axes), with or without antialiasing, evaluated in fp64.
+ * For one axis with input length n and scale s:
+ *   m = ceil(n s) in doubles; kw = 4 / s when s < 1 and antialias != 0, else 4; T = ceil(kw) taps per output.
+ *   For output k = 1 .. m (1-based): u = k / s + 0.5 (1 - 1 / s), left = floor(u - kw / 2), taps j = left + 1 .. left + T,
+ *   v_j = s c(s (u - j)) under antialiasing, c(u - j) otherwise, c Keys' cubic with a = -0.5 in the order of operations
+ *   written out in ssg_imresize.hip; w_j = v_j / (the sum of the v_j in index order).  All fp64, no fused multiply-add.
+ *   A tap outside the image is mirrored symmetrically ON THE INDEX: 0-based j < 0 reads -1 - j, j >= n reads 2 n - 1 - j.
+ *   Every tap must reach the image with one reflection, -n <= j <= 2 n - 1 (the reference's padding copy raises
+ *   outside that): such an axis is refused with SSG_E_IMAGESMALL.
+ *   The columns are filtered first, into fp64; the rows are filtered from that: fp64 sums in tap order from 0.0.
+ * ssg_imresize_out_size: m, or SSG_E_BADARG (n < 1, scale <= 0, not finite, or n s = 0) / SSG_E_TOOLARGE (m >= 2^31).
+ * ssg_imresize_taps: T, or SSG_E_BADARG (scale) / SSG_E_TOOLARGE (T > 32: antialiased scales below 1 / 8).
+ * ssg_imresize_table: HOST function, no device.  first[m] = left (the first tap's 0-based index, before the mirror),
+ *   weights[m][T].  m must be ssg_imresize_out_size(n, scale) (SSG_E_BADARG otherwise); the statuses of the two
+ *   functions above, and SSG_E_IMAGESMALL for the mirror domain, with both arrays untouched.
+ * ssg_imresize_tiles: writes the (rows, columns) of up to `capacity` tiles of the kernel's list, returns how many the
+ *   list has, and with `chosen` non-null the index of the tile a call at (scale, antialias) takes (-1: invalid scale, too
+ *   many taps).
+ * ssg_imresize: one launch for B C planes.  in_kind SSG_IMRESIZE_IN_F32: src fp32 (B,C,Hin,Win), any C >= 1, out_kind
+ *   SSG_IMRESIZE_F32_PLANES: (float)y, fp32 (B,C,Hout,Wout), rounded once.  in_kind SSG_IMRESIZE_IN_U8_HWC: src uint8
+ *   (B,Hin,Win,C), C 1 or 3, y summed over the byte values 0 .. 255 themselves; out_kind SSG_IMRESIZE_U8_HWC the byte
+ *   v = min(255, floor(y + 0.5)) for y >= 0 and 0 below (MATLAB's round-half-away on uint8), uint8 (B,Hout,Wout,C), or
+ *   SSG_IMRESIZE_F32_UNIT (float)v / 255.0f, fp32 (B,C,Hout,Wout) (what ssg_edge_mask_laplacian takes).  The four
+ *   tables are those of ssg_imresize_table for (Hin, Hout) and (Win, Wout), on the device.  A workgroup of 256 threads
+ *   per output tile and plane reads the tile's mirrored footprint into LDS as fp32, filters the columns into an fp64
+ *   intermediate in LDS and the rows from that.  No atomics: plane b of a batch gets the bits it gets alone, and a
+ *   repeat gives the same bits.  No allocation, synchronisation or host read.
+ * Status, decided before the launch with the output untouched: SSG_E_BADARG for a null pointer, out == src, B, C or a
+ * size < 1, C not 1 or 3 for bytes, an unknown kind or a pair of kinds not listed above, a scale <= 0 or not finite;
+ * SSG_E_TOOLARGE for more than 32 taps or 2^31 input or output elements and more; SSG_E_IMAGESMALL for a side outside
+ * the mirror domain.  Every upscale and every non-antialiased scale has four taps and is in the domain: where the taps
+ * of neighbouring outputs lie further apart than they are wide, the footprint holds four entries per output. */
+#define SSG_IMRESIZE_IN_F32 0
+#define SSG_IMRESIZE_IN_U8_HWC 1
+#define SSG_IMRESIZE_F32_PLANES 0
+#define SSG_IMRESIZE_U8_HWC 1
+#define SSG_IMRESIZE_F32_UNIT 2
+int ssg_imresize_out_size(int n, double scale);
+int ssg_imresize_taps(double scale, int antialias);
+int ssg_imresize_table(int n, int m, double scale, int antialias, int *first, double *weights);
+int ssg_imresize_tiles(double scale, int antialias, int *tiles, int capacity, int *chosen /* nullable */);
+int ssg_imresize(const void *src, int in_kind, int B, int C, int Hin, int Win, double scale, int antialias,
+                 const int *yfirst, const double *yweights, const int *xfirst, const double *xweights, int out_kind,
+                 void *out, ssg_stream_t stream);
 
 #ifdef SSG_PROFILE
 /* PROFILING BUILD ONLY (libssg_hip_prof.so, compiled with -DSSG_PROFILE; the product library libssg_hip.so does not

@@ -100,6 +100,11 @@ PROTOTYPES = {
     "ssg_resample_tile": (_i, [_vp, _vp]),
     "ssg_resample_max_ratio": (_i, []),
     "ssg_resample": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp]),
+    "ssg_imresize_out_size": (_i, [_i, ctypes.c_double]),
+    "ssg_imresize_taps": (_i, [ctypes.c_double, _i]),
+    "ssg_imresize_table": (_i, [_i, _i, ctypes.c_double, _i, _vp, _vp]),
+    "ssg_imresize_tiles": (_i, [ctypes.c_double, _i, _vp, _i, _vp]),
+    "ssg_imresize": (_i, [_vp, _i, _i, _i, _i, _i, ctypes.c_double, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp]),
     # include/similarity.h: the reference operator's own (void, stream-less) interface
     "ssg_ref_compute_similarity": (None, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i]),
     "ssg_ref_compute_similarity_backward": (None, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i]),

@@ -129,6 +129,15 @@ int launch_resample(const uint8_t *src, int B, int C, int Hin, int Win, int Hout
                     const int *xbounds, const int *xcoef, const int *ybounds, const int *ycoef, int out_kind, void *out,
                     hipStream_t st);
 
+// ---- ssg_imresize.hip: MATLAB's bicubic imresize in fp64 (entry points beside its kernel) ----
+int imresize_out_size(int n, double scale);                                        // host only
+int imresize_taps(double scale, int antialias);                                    // host only
+int imresize_table(int n, int m, double scale, int antialias, int *first, double *weights);   // host only: fp64
+int imresize_tiles(double scale, int antialias, int *tiles, int capacity, int *chosen);
+int launch_imresize(const void *src, int in_kind, int B, int C, int Hin, int Win, double scale, int antialias,
+                    const int *yfirst, const double *yweights, const int *xfirst, const double *xweights, int out_kind,
+                    void *out, hipStream_t st);
+
 // ---- ssg_api.hip ----
 // host-mapped {rows for the direct kernels, dense tiles} of the device's last plan, written by the edge-list builder's
 // scan kernel (nullptr: no hint wanted, or none allocated yet and `st` is being captured)

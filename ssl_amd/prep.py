@@ -1,4 +1,5 @@
-"""Pillow-exact image resize and the dataset preparation around it, on the GPU (ssl_amd/csrc/ssg_resample.hip).
+"""Pillow-exact image resize, MATLAB's bicubic imresize and the dataset preparation around them, on the GPU
+(ssl_amd/csrc/ssg_resample.hip, ssl_amd/csrc/ssg_imresize.hip).
 
 `resize` is `PIL.Image.resize(size, resample)` for 8-bit 'L' and 'RGB' images and the five convolution filters, byte for
 byte (the algorithm is integer from its coefficient tables on; the tables are computed on the host in fp64 with the C
@@ -9,6 +10,10 @@ library's sin / cos, as Pillow's C code computes them, and cached per (in, out, 
 * `multiscale` / `multiscale_plan`: generate_multiscale_img.py ('gan') and generate_multiscale_DF2K.py ('dm');
 * `subimage_grid` / `extract_subimages`: extract_subimages.py:82-99.
 
+`imresize` (alias `imresize_np`) is the reference's `basicsr.utils.matlab_functions.imresize` / KAIR's
+`utils_image.imresize(_np)`: MATLAB's bicubic imresize for any scale, with or without antialiasing, evaluated in fp64
+(include/ssg_hip.h section (O)); `modcrop` is generate_bicubic_img.m's.
+
 Contract: include/ssg_hip.h section (N).  Images are uint8 tensors on the GPU, (H,W), (H,W,C) or (B,H,W,C) with C 1 or 3;
 decoding and encoding image files stay on the CPU (PIL), there is no CPU path for the resize itself."""
 import numpy as np
@@ -18,7 +23,7 @@ from . import _lib
 from .engine import _launch, _need_gpu, _ptr
 
 __all__ = ["resize", "load_img", "from_pil", "multiscale", "multiscale_plan", "subimage_grid", "extract_subimages",
-           "subimage_name", "FILTERS"]
+           "subimage_name", "FILTERS", "imresize", "imresize_np", "modcrop"]
 
 FILTERS = {'lanczos': 1, 'bilinear': 2, 'bicubic': 3, 'box': 4, 'hamming': 5}      # Pillow's Image.Resampling numbers
 _OUT = {'uint8': 0, 'unit': 1, 'signed': 2}
@@ -212,3 +217,152 @@ def subimage_name(name, index, extension):
     """{name}_s{index:03d}{extension} with 'x2', 'x3', 'x4', 'x8' removed from the name (extract_subimages.py:75-78,97)."""
     name = name.replace('x2', '').replace('x3', '').replace('x4', '').replace('x8', '')
     return f"{name}_s{index:03d}{extension}"
+
+
+# -------------------------------------------------------------------------------------------- MATLAB's imresize ---
+_imresize_tables = {}
+
+
+def _imresize_scale(scale):
+    try:
+        s = float(scale)
+    except (TypeError, ValueError):
+        raise ValueError(f"ssl_amd: imresize takes a positive finite scale, got {scale!r}") from None
+    if not (s > 0.0 and s != float("inf")):
+        raise ValueError(f"ssl_amd: imresize takes a positive finite scale, got {scale!r}")
+    return s
+
+
+def imresize_host_table(n, scale, antialiasing=True):
+    """(first (m,) int32, weights (m, taps) float64) of one axis from the library's host function: the first tap's
+    0-based index before the mirror, and the normalised fp64 weights.  Raises for what the library refuses."""
+    L = _lib.lib()
+    s, aa = _imresize_scale(scale), int(bool(antialiasing))
+    taps = L.ssg_imresize_taps(s, aa)
+    if taps == -2:
+        raise NotImplementedError(f"ssl_amd: imresize takes at most 32 taps per output, that is antialiased scales "
+                                  f"down to 1 / 8; scale {s} needs {int(np.ceil(4 / s))}")
+    m = L.ssg_imresize_out_size(n, s)
+    if m == -2:
+        raise ValueError(f"ssl_amd: imresize of a side of {n} by {s} has 2^31 pixels or more")
+    _lib.check(min(taps, m, 0))
+    first = np.empty(m, np.int32)
+    weights = np.empty((m, taps), np.float64)
+    rc = L.ssg_imresize_table(n, m, s, aa, first.ctypes.data, weights.ctypes.data)
+    if rc == -4:
+        raise ValueError(f"ssl_amd: imresize by {s} on a side of {n} pixels reaches past one mirror of the image (every "
+                         f"tap must lie in [1 - {n}, {2 * n}], as the reference's padding needs); the side is too small")
+    _lib.check(rc)
+    return first, weights
+
+
+def _imresize_table(n, scale, aa, dev=None):
+    """the tables of one axis, cached per (n, m, scale, antialiasing, device); dev None: the host's, which every call
+    asks for first, so that a refusal is raised before anything touches the GPU"""
+    m = _lib.lib().ssg_imresize_out_size(n, scale)
+    key = (n, m, scale, aa, dev)
+    if key not in _imresize_tables:
+        host = imresize_host_table(n, scale, aa) if dev is None else _imresize_table(n, scale, aa)
+        _imresize_tables[key] = host if dev is None else tuple(torch.from_numpy(t).to(dev) for t in host)
+    return _imresize_tables[key]
+
+
+def _imresize_launch(x, in_kind, B, C, H, W, s, aa, out_kind):
+    """x contiguous on the GPU, float32 (B,C,H,W) or uint8 (B,H,W,C) -> the kernel's output tensor"""
+    L = _lib.lib()
+    dev = x.device
+    yf, yw = _imresize_table(H, s, aa, dev)
+    xf, xw = _imresize_table(W, s, aa, dev)
+    h, w = yf.numel(), xf.numel()
+    if out_kind == 1:
+        res = torch.empty((B, h, w, C), dtype=torch.uint8, device=dev)
+    else:
+        res = torch.empty((B, C, h, w), dtype=torch.float32, device=dev)
+    _launch(dev, L.ssg_imresize, _ptr(x), in_kind, B, C, H, W, s, int(aa), _ptr(yf), _ptr(yw), _ptr(xf), _ptr(xw),
+            out_kind, _ptr(res))
+    return res
+
+
+def imresize(img, scale, antialiasing=True, out=None):
+    """MATLAB's bicubic imresize as the reference's `imresize(img, scale, antialiasing=True)` restates it, in fp64 on
+    the GPU; output sides are ceil(side * scale).
+
+    * numpy float (H,W) / (H,W,C)                      -> numpy float32 of the same layout (computed on the current GPU)
+    * floating GPU tensor (H,W) / (C,H,W) / (B,C,H,W)  -> float32 tensor of the same layout, "w/o round"
+      (float16 / bfloat16 / float64 are computed from their float32 cast)
+    * uint8 GPU tensor (H,W) / (H,W,C) / (B,H,W,C), C 1 or 3 -> uint8 of the same layout, min(255, floor(y + 0.5)) with
+      y summed over the bytes themselves (MATLAB's rounding on uint8); `out='unit'` returns float32 (B,C,h,w) byte / 255.
+    A CPU tensor raises RuntimeError (there is no CPU path); a scale <= 0, a side too small for one mirror, 2^31 elements
+    and a channel count other than 1 or 3 raise ValueError; more than 32 taps raises NotImplementedError."""
+    s = _imresize_scale(scale)
+    aa = bool(antialiasing)
+    if isinstance(img, np.ndarray):
+        if not np.issubdtype(img.dtype, np.floating):
+            raise TypeError(f"ssl_amd: imresize takes a numpy float image (the reference's [0, 1] range), got {img.dtype}; "
+                            "pass bytes as a uint8 GPU tensor")
+        if img.ndim not in (2, 3):
+            raise ValueError(f"ssl_amd: imresize takes a numpy (H,W) or (H,W,C) image, got {img.shape}")
+        if out is not None:
+            raise ValueError("ssl_amd: imresize out is for uint8 tensors; a float image gives float32")
+        x = torch.from_numpy(np.ascontiguousarray(img[:, :, None] if img.ndim == 2 else img).astype(np.float32))
+        y = imresize(x.permute(2, 0, 1).to(_current_device()), s, aa).permute(1, 2, 0).cpu().numpy()
+        return np.ascontiguousarray(y[:, :, 0] if img.ndim == 2 else y)
+    if not torch.is_tensor(img):
+        raise TypeError("ssl_amd: imresize takes a numpy float image, a floating GPU tensor or a uint8 GPU tensor")
+    if img.dtype == torch.uint8:
+        if out not in (None, 'uint8', 'unit'):
+            raise ValueError(f"ssl_amd: imresize out is None, 'uint8' or 'unit' for bytes, got {out!r}")
+        if img.dim() not in (2, 3, 4):
+            raise ValueError(f"ssl_amd: imresize takes uint8 (H,W), (H,W,C) or (B,H,W,C), got {tuple(img.shape)}")
+        x = img[..., None] if img.dim() == 2 else img
+        x = x[None] if x.dim() == 3 else x
+        B, H, W, C = x.shape
+        if C not in (1, 3):
+            raise ValueError(f"ssl_amd: imresize takes 1 ('L') or 3 ('RGB') channels last for bytes, got {C}")
+        in_kind, out_kind = 1, (2 if out == 'unit' else 1)
+    elif img.is_floating_point():
+        if out is not None:
+            raise ValueError(f"ssl_amd: imresize out is for uint8 tensors; a float tensor gives float32, got out={out!r}")
+        if img.dim() not in (2, 3, 4):
+            raise ValueError(f"ssl_amd: imresize takes float (H,W), (C,H,W) or (B,C,H,W), got {tuple(img.shape)}")
+        x = img.reshape((1,) * (4 - img.dim()) + tuple(img.shape))
+        B, C, H, W = x.shape
+        in_kind, out_kind = 0, 0
+    else:
+        raise TypeError(f"ssl_amd: imresize takes floating or uint8 tensors, got {img.dtype}")
+    if min(B, C, H, W) < 1:
+        raise ValueError(f"ssl_amd: imresize got an empty image {tuple(img.shape)}")
+    h, w = (len(_imresize_table(n, s, aa)[0]) for n in (H, W))        # raises what the library refuses of an axis
+    if max(B * C * H * W, B * C * h * w) > 2 ** 31 - 1:
+        raise ValueError("ssl_amd: imresize takes at most 2^31 - 1 elements per call, input and output")
+    _need_gpu(img)
+    x = x.detach().to(torch.float32).contiguous() if in_kind == 0 else x.contiguous()
+    res = _imresize_launch(x, in_kind, B, C, H, W, s, aa, out_kind)
+    if out_kind == 2:
+        return res
+    if in_kind == 0:
+        return res.reshape(tuple(img.shape[:-2]) + (h, w))
+    res = res if img.dim() == 4 else res[0]
+    return res[..., 0] if img.dim() == 2 else res
+
+
+imresize_np = imresize
+
+
+def modcrop(img, modulo):
+    """generate_bicubic_img.m's modcrop: the sides cut down to a multiple of `modulo` (a view).  numpy (H,W) / (H,W,C),
+    uint8 tensors (H,W) / (H,W,C) / (B,H,W,C), floating tensors (H,W) / (C,H,W) / (B,C,H,W)."""
+    if isinstance(modulo, bool) or not isinstance(modulo, (int, np.integer)) or modulo < 1:
+        raise ValueError(f"ssl_amd: modcrop takes an integer modulo >= 1, got {modulo!r}")
+    nd = img.ndim if isinstance(img, np.ndarray) else img.dim()
+    if nd not in (2, 3, 4) or (isinstance(img, np.ndarray) and nd == 4):
+        raise ValueError(f"ssl_amd: modcrop takes the layouts of imresize, got {tuple(img.shape)}")
+    channels_last = isinstance(img, np.ndarray) or img.dtype == torch.uint8
+    ay = (0 if nd < 4 else 1) if channels_last else nd - 2
+    H, W = img.shape[ay], img.shape[ay + 1]
+    h, w = H - H % modulo, W - W % modulo
+    if h == 0 or w == 0:
+        raise ValueError(f"ssl_amd: modcrop by {modulo} of a {H} x {W} image leaves none of it")
+    index = [slice(None)] * nd
+    index[ay], index[ay + 1] = slice(0, h), slice(0, w)
+    return img[tuple(index)]
