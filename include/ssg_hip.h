@@ -68,6 +68,8 @@ typedef void *ssg_stream_t; /* hipStream_t */
 /* 6, additive: + ssg_synth_kernels and its record (the degradation chain's blur and sinc kernels, section (I)). */
 /* 6, additive: + ssg_resample, ssg_resample_table / _ksize / _tile / _max_ratio (Pillow's 8-bit resize, section (N)). */
 /* 6, additive: + ssg_imresize, ssg_imresize_out_size / _taps / _table / _tiles (MATLAB's bicubic imresize, section (O)). */
+/* 6, additive: + ssg_jpeg_roundtrip, ssg_jpeg_roundtrip_workspace_bytes, ssg_jpeg_unit_table (libjpeg's baseline round
+ * trip, section (P)); nothing existing changed, so the version number stays. */
 int ssg_abi_version(void);
 const char *ssg_status_string(int status);
 /* Device-side refusals that no return value can carry (everything is asynchronous): waits for `stream`, then returns
@@ -849,6 +851,39 @@ int ssg_imresize_tiles(double scale, int antialias, int *tiles, int capacity, in
 int ssg_imresize(const void *src, int in_kind, int B, int C, int Hin, int Win, double scale, int antialias,
                  const int *yfirst, const double *yweights, const int *xfirst, const double *xweights, int out_kind,
                  void *out, ssg_stream_t stream);
+
+/* ---------------------------------------------------------------- (P) ----
+ * libjpeg's baseline JPEG round trip, encode at a quality and decode again, without the bitstream: what the reference
+ * reaches through cv2.imencode / cv2.imdecode (KAIR's utils_blindsr.py:412-418 add_JPEG_noise, basicsr's
+ * degradations.py add_jpg_compression, scripts/util_image.py:366-383 jpeg_compress), ssl_amd/csrc/ssg_jpegcodec.hip.
+ * jpeg_set_quality(quality, force_baseline), 4:2:0 for colour, the "islow" integer DCT pair, fancy upsampling, no
+ * smoothing: the eight integer stages written out at the top of ssg_jpegcodec.hip and restated in
+ * tests/jpeg_codec_reference.py, to which the result is EQUAL, byte for byte, for every H, W >= 1.
+ * ssg_jpeg_roundtrip: `in` SSG_JPEG_IN_U8_HWC uint8 (B,H,W,channels), or SSG_JPEG_IN_F32_NCHW fp32 (B,channels,H,W)
+ *   quantised as rint(min(max(x, 0), 1) 255.0f) (round half to even); channels 1 (grey) or 3 (RGB).  `qualities`: B ints
+ *   1 .. 100 on the HOST, read before the call returns (they travel as kernel arguments, 256 images a launch).  `out`
+ *   SSG_JPEG_OUT_U8_HWC the bytes, uint8 (B,H,W,channels), or SSG_JPEG_OUT_F32_NCHW fp32 (B,channels,H,W) holding
+ *   (float)((double)v / 255.0), the 256 values ssg_jpeg_unit_table writes (numpy's float32(v / 255.)).
+ *   A workgroup of 256 threads codes a tile of 32 x 32 pixels in LDS.  The chroma upsampling reads one sample beyond the
+ *   tile, so a colour call writes the reconstructed Y, Cb and Cr bytes to `workspace` and upsamples and converts in a
+ *   second launch (measured against one launch that recomputes the chroma blocks around each tile:
+ *   profiles/jpeg_codec_tile_ab.txt); a grey call is one launch and takes no workspace (`workspace` may be NULL).
+ *   ssg_jpeg_roundtrip_workspace_bytes: B (H W + 2 ceil(H / 2) ceil(W / 2)) bytes with each image's share rounded up to
+ *   256 for channels = 3, 0 for channels = 1 (and for arguments the call would refuse).
+ *   No atomics: image b of a batch gets the bytes it gets alone, and a repeat gives the same bytes.  No allocation,
+ *   synchronisation or device read of host memory.
+ * Status, decided before the launch with the output untouched: SSG_E_BADARG for a null in, out or qualities, out == in,
+ * a null workspace where one is needed, B or a size < 1, channels not 1 or 3, an unknown layout or epilogue, a quality
+ * outside 1 .. 100; SSG_E_TOOLARGE for 2^31 elements or more; SSG_E_WORKSPACE for a workspace smaller than
+ * ssg_jpeg_roundtrip_workspace_bytes(); SSG_E_ALIGN for one that is not 16-byte aligned. */
+#define SSG_JPEG_IN_U8_HWC 0
+#define SSG_JPEG_IN_F32_NCHW 1
+#define SSG_JPEG_OUT_U8_HWC 0
+#define SSG_JPEG_OUT_F32_NCHW 1
+size_t ssg_jpeg_roundtrip_workspace_bytes(int B, int H, int W, int channels);
+int ssg_jpeg_unit_table(float *table /* 256 floats, host */);
+int ssg_jpeg_roundtrip(const void *in, void *out, int B, int H, int W, int channels, const int *qualities,
+                       int in_layout, int out_epilogue, void *workspace, size_t workspace_bytes, ssg_stream_t stream);
 
 #ifdef SSG_PROFILE
 /* PROFILING BUILD ONLY (libssg_hip_prof.so, compiled with -DSSG_PROFILE; the product library libssg_hip.so does not

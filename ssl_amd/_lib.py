@@ -105,6 +105,9 @@ PROTOTYPES = {
     "ssg_imresize_table": (_i, [_i, _i, ctypes.c_double, _i, _vp, _vp]),
     "ssg_imresize_tiles": (_i, [ctypes.c_double, _i, _vp, _i, _vp]),
     "ssg_imresize": (_i, [_vp, _i, _i, _i, _i, _i, ctypes.c_double, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp]),
+    "ssg_jpeg_roundtrip_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "ssg_jpeg_unit_table": (_i, [_vp]),
+    "ssg_jpeg_roundtrip": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, _i, _vp, _sz, _vp]),
     # include/similarity.h: the reference operator's own (void, stream-less) interface
     "ssg_ref_compute_similarity": (None, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i]),
     "ssg_ref_compute_similarity_backward": (None, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i]),

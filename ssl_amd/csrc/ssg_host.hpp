@@ -138,6 +138,12 @@ int launch_imresize(const void *src, int in_kind, int B, int C, int Hin, int Win
                     const int *yfirst, const double *yweights, const int *xfirst, const double *xweights, int out_kind,
                     void *out, hipStream_t st);
 
+// ---- ssg_jpegcodec.hip: libjpeg's baseline round trip in integers (entry points beside its kernels) ----
+size_t jpeg_roundtrip_workspace_bytes(int B, int H, int W, int channels);
+int jpeg_unit_table(float *table);                                                 // host only
+int launch_jpeg_roundtrip(const void *in, void *out, int B, int H, int W, int channels, const int *qualities,
+                          int in_layout, int out_epilogue, void *workspace, size_t workspace_bytes, hipStream_t st);
+
 // ---- ssg_api.hip ----
 // host-mapped {rows for the direct kernels, dense tiles} of the device's last plan, written by the edge-list builder's
 // scan kernel (nullptr: no hint wanted, or none allocated yet and `st` is being captured)

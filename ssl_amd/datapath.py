@@ -200,6 +200,147 @@ class DiffJPEG(torch.nn.Module):
         return out.to(x.dtype)
 
 
+# ------------------------------------------------------------------ the real codec: libjpeg's round trip ----
+def _jpeg_qualities(quality, B):
+    """B ints 1 .. 100 as an int32 numpy array (what the C ABI reads on the host), from an int or B of them"""
+    if torch.is_tensor(quality):
+        quality = quality.detach().cpu().numpy()
+    q = np.asarray(quality)
+    if q.dtype.kind not in "iuf":                   # (bools, strings, None and ragged lists end here)
+        raise ValueError(f"ssl_amd: a JPEG quality is an integer 1 .. 100, got {quality!r}")
+    if q.ndim == 0:
+        q = np.full(B, q)
+    if q.ndim != 1 or q.size != B:
+        raise ValueError(f"ssl_amd: jpeg_roundtrip takes one quality or one per image ({B}), got shape {q.shape}")
+    if not bool(((q == np.floor(q)) & (q >= 1) & (q <= 100)).all()):
+        raise ValueError(f"ssl_amd: a JPEG quality is an integer 1 .. 100, got {quality!r}")
+    return np.ascontiguousarray(q, dtype=np.int32)
+
+
+def _jpeg_device():
+    """where a numpy image goes: the current GPU"""
+    if not torch.cuda.is_available():
+        raise RuntimeError("ssl_amd.datapath: the JPEG round trip runs on the GPU and none is visible; there is no CPU path")
+    return torch.device("cuda", torch.cuda.current_device())
+
+
+def _jpeg_call(x, B, H, W, C, quality, in_f32, out_f32):
+    """one ssg_jpeg_roundtrip on contiguous `x` (uint8 (B,H,W,C) or float32 (B,C,H,W))"""
+    if not x.is_cuda:
+        raise RuntimeError("ssl_amd.datapath.jpeg_roundtrip: tensor must be on the GPU (there is no CPU path)")
+    if B < 1 or H < 1 or W < 1:
+        raise ValueError(f"ssl_amd: jpeg_roundtrip got an empty image {tuple(x.shape)}")
+    if B * H * W * C > 2 ** 31 - 1:
+        raise ValueError("ssl_amd: jpeg_roundtrip takes at most 2^31 - 1 elements per call")
+    qs = _jpeg_qualities(quality, B)
+    L = _lib.lib()
+    out = torch.empty((B, C, H, W) if out_f32 else (B, H, W, C), dtype=torch.float32 if out_f32 else torch.uint8,
+                      device=x.device)
+    nbytes = L.ssg_jpeg_roundtrip_workspace_bytes(B, H, W, C)
+    ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=x.device)
+    with torch.cuda.device(x.device):
+        _lib.check(L.ssg_jpeg_roundtrip(_ptr(x), _ptr(out), B, H, W, C, qs.ctypes.data, int(in_f32), int(out_f32),
+                                        _ptr(ws), nbytes, _stream()))
+    return out
+
+
+@torch.no_grad()
+def jpeg_roundtrip(img, quality):
+    """libjpeg's baseline JPEG encode at `quality` and decode again (4:2:0, the integer "islow" DCT, fancy upsampling:
+    what `cv2.imencode('.jpg', ...)` + `cv2.imdecode` and Pillow's `save(format='JPEG', quality=q)` + `open` give), on
+    the HIP engine (ssg_jpeg_roundtrip), equal to tests/jpeg_codec_reference.py byte for byte.  `img`: a GPU tensor,
+    uint8 (H,W,3), (B,H,W,3), (H,W) or (B,H,W) -- RGB order or grey -- or floating (B,1|3,H,W) in [0, 1], quantised as
+    `uint8((clip(x, 0, 1) * 255).round())` and returned as `float32(v / 255.)` cast to its dtype.  `quality`: an int
+    1 .. 100, or B of them (list, tuple, array or tensor).  The same dtype and layout come back.  Not differentiable
+    (`DiffJPEG` is the simulation training differentiates around); the result carries no graph."""
+    if not torch.is_tensor(img):
+        raise TypeError("ssl_amd: jpeg_roundtrip takes a GPU tensor (uint8 pixels or floats in [0, 1])")
+    if img.dtype == torch.uint8:
+        if img.dim() == 2:
+            x = img[None, :, :, None]
+        elif img.dim() == 3:
+            x = img[None] if img.shape[-1] == 3 else img[..., None]
+        elif img.dim() == 4 and img.shape[-1] == 3:
+            x = img
+        else:
+            raise ValueError(f"ssl_amd: jpeg_roundtrip takes uint8 (H,W), (B,H,W), (H,W,3) or (B,H,W,3), got "
+                             f"{tuple(img.shape)}")
+        B, H, W, C = x.shape
+        return _jpeg_call(x.detach().contiguous(), B, H, W, C, quality, False, False).reshape(img.shape)
+    if not img.is_floating_point():
+        raise TypeError(f"ssl_amd: jpeg_roundtrip takes uint8 or floating tensors, got {img.dtype}")
+    if img.dim() != 4 or img.shape[1] not in (1, 3):
+        raise ValueError(f"ssl_amd: jpeg_roundtrip takes float (B,1,H,W) or (B,3,H,W), got {tuple(img.shape)}")
+    B, C, H, W = img.shape
+    return _jpeg_call(img.detach().to(torch.float32).contiguous(), B, H, W, C, quality, True, True).to(img.dtype)
+
+
+def _jpeg_hwc_float(img, quality, what, bgr=False):
+    """The reference's float (H,W,3) images in [0, 1] through the codec: numpy (moved to the current GPU and back) or a
+    GPU tensor.  Quantised in the image's own dtype as `((clip(x, 0, 1) * 255.).round())` (half to even) -- in the
+    kernel for float32, by torch otherwise -- and returned as float32 `v / 255.`."""
+    is_np = isinstance(img, np.ndarray)
+    if is_np:
+        x = torch.from_numpy(np.ascontiguousarray(img)).to(_jpeg_device())
+    elif torch.is_tensor(img):
+        x = img.detach()
+    else:
+        raise TypeError(f"ssl_amd: {what} takes a numpy array or a GPU tensor, got {type(img).__name__}")
+    if not x.is_floating_point():
+        raise TypeError(f"ssl_amd: {what} takes a float image in [0, 1], got {x.dtype}")
+    if x.dim() != 3 or x.shape[2] != 3:
+        raise ValueError(f"ssl_amd: {what} takes an (H,W,3) image, got {tuple(x.shape)}")
+    H, W, _ = x.shape
+    if bgr:
+        x = x.flip(-1)
+    if x.dtype == torch.float32:
+        y = _jpeg_call(x.permute(2, 0, 1)[None].contiguous(), 1, H, W, 3, quality, True, True)
+    else:
+        u8 = (x.clamp(0, 1) * 255.).round().to(torch.uint8)
+        y = _jpeg_call(u8[None].contiguous(), 1, H, W, 3, quality, False, True)
+    y = y[0].permute(1, 2, 0)
+    y = (y.flip(-1) if bgr else y).contiguous()
+    return y.cpu().numpy() if is_np else y
+
+
+def add_JPEG_noise(img, quality_factor=None, draws=None):
+    """KAIR's `add_JPEG_noise` (utils_blindsr.py:412-418; the copies in utils_parameter_blindsr.py and the diffusion
+    fork's bsrgan.py / bsrgan_light.py): float RGB (H,W,3) in [0, 1] through `single2uint`, the codec at a quality drawn
+    as `random.randint(75, 95)` (through `draws.randint`, a `Draws`, when `quality_factor` is not given) and
+    `uint2single`.  The reference's RGB -> BGR -> RGB swaps around cv2 cancel and are not performed."""
+    if quality_factor is None:
+        quality_factor = (draws if draws is not None else Draws()).randint(75, 95)
+    return _jpeg_hwc_float(img, quality_factor, "add_JPEG_noise")
+
+
+def add_jpg_compression(img, quality=90):
+    """basicsr's `add_jpg_compression` (degradations.py): float (H,W,3) in [0, 1], in cv2's BGR order as basicsr keeps
+    its images, clipped, through the codec, `float32(v) / 255.`.  The reference hands `img * 255.` to cv2 as floats;
+    the conversion to bytes is taken to be round-half-to-even.  `quality` goes through `int()`, as the
+    diffusion fork's copy does for the float that `random_add_jpg_compression` draws."""
+    if isinstance(quality, (float, np.floating)) and math.isfinite(quality):
+        quality = int(quality)
+    return _jpeg_hwc_float(img, quality, "add_jpg_compression", bgr=True)
+
+
+def jpeg_compress(im, qf, chn_in='rgb'):
+    """scripts/util_image.py:366-383 `jpeg_compress`: (H,W,3) uint8 or float in [0, 1], RGB or BGR (`chn_in`), the same
+    dtype and order out.  numpy (moved to the current GPU and back) or a GPU tensor."""
+    if chn_in.lower() not in ('rgb', 'bgr'):
+        raise ValueError(f"ssl_amd: jpeg_compress takes chn_in 'rgb' or 'bgr', got {chn_in!r}")
+    bgr = chn_in.lower() == 'bgr'
+    dtype = im.dtype if isinstance(im, np.ndarray) or torch.is_tensor(im) else None
+    if dtype in (np.dtype('uint8'), torch.uint8):
+        is_np = isinstance(im, np.ndarray)
+        x = torch.from_numpy(np.ascontiguousarray(im)).to(_jpeg_device()) if is_np else im
+        if x.dim() != 3 or x.shape[2] != 3:
+            raise ValueError(f"ssl_amd: jpeg_compress takes an (H,W,3) image, got {tuple(x.shape)}")
+        y = jpeg_roundtrip(x.flip(-1) if bgr else x, qf)
+        y = (y.flip(-1) if bgr else y).contiguous()
+        return y.cpu().numpy() if is_np else y
+    y = _jpeg_hwc_float(im, qf, "jpeg_compress", bgr=bgr)
+    return y.astype(im.dtype) if isinstance(im, np.ndarray) else y.to(im.dtype)
+
 
 # ------------------------------------------------------------------ the rest of the degradation chain ----
 _RESIZE_MODES = {"area": 0, "bilinear": 1, "bicubic": 2}
