@@ -1,4 +1,10 @@
-"""ctypes binding of libssg_hip.so (include/ssg_hip.h).
+"""ctypes binding of libssg_hip.so, read from the headers the library ships with.
+
+include/ssg_hip.h and include/similarity.h are the contract, and this module states none of it a second time:
+``read_header`` turns their declarations into ``PROTOTYPES`` (name -> (restype, [argtypes])), the declarations inside
+``#ifdef SSG_PROFILE`` into ``PROF_PROTOTYPES`` (libssg_hip_prof.so only) and the ``#define SSG_<NAME> <integer>`` lines
+into ``CONSTANTS``, at import, with ``re`` and ``ctypes`` alone.  A declaration it cannot type raises, with the
+function's name and the text: nothing defaults to a pointer or an int.
 
 The shared library is built in-tree by ``ssl_amd._lib.build()`` (hipcc,
 --offload-arch=gfx950; cross-compiles without a GPU) and travels with the
@@ -7,6 +13,7 @@ absent, importing the compute path raises.
 """
 import ctypes
 import os
+import re
 import subprocess
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -16,111 +23,65 @@ SO_PATH = os.path.join(CSRC, "libssg_hip.so")
 # tools/); the product library above has neither
 PROF_SO_PATH = os.path.join(CSRC, "libssg_hip_prof.so")
 HEADER = os.path.join(os.path.dirname(_HERE), "include", "ssg_hip.h")
+# the reference operator's own (void, stream-less) interface and ssg_last_status
+REF_HEADER = os.path.join(os.path.dirname(HEADER), "similarity.h")
 
-_vp, _i, _f, _sz = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_size_t
+_SCALARS = {"int": ctypes.c_int, "float": ctypes.c_float, "double": ctypes.c_double, "size_t": ctypes.c_size_t,
+            "unsigned": ctypes.c_uint, "ssg_stream_t": ctypes.c_void_p}
+_RETURNS = dict(_SCALARS, **{"void": None, "const char *": ctypes.c_char_p})
 
-# name -> (restype, argtypes); mirrors include/ssg_hip.h one to one
-PROTOTYPES = {
-    "ssg_abi_version": (_i, []),
-    "ssg_status_string": (ctypes.c_char_p, [_i]),
-    "ssg_compute_similarity": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
-    "ssg_compute_similarity_backward": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
-    "ssg_edge_scratch_bytes": (_sz, [_i, _i, _i]),
-    "ssg_forward_plan_bytes": (_sz, [_i, _i, _i, _i]),
-    "ssg_set_dense_threshold": (_i, [_i]),
-    "ssg_set_overlap": (_i, [_i]),
-    "ssg_last_overlap_assignment": (_i, []),
-    "ssg_set_tiny_step": (_i, [_i]),
-    "ssg_edge_list": (_i, [_vp, _i, _i, _i, _i, _i, _i, _f, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "ssg_edge_mask_laplacian": (_i, [_vp, _i, _i, _i, _f, _i, _vp, _vp]),
-    "ssg_map_forward": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _f, _i, _vp, _vp,
-                             _vp, _vp]),
-    "ssg_backward_scratch_bytes": (_sz, [_i, _i]),
-    "ssg_map_backward": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _i, _vp, _vp, _vp, _vp,
-                              _vp, _vp]),
-    "ssg_grad_fix_bytes": (_sz, [_i, _i, _i, _i]),
-    "ssg_loss_scratch_bytes": (_sz, [_i, _i, _i, _i, _i]),
-    "ssg_loss_backward": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _f, _i, _vp, _vp, _f, _f,
-                               _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp]),
-    "ssg_loss_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
-    "ssg_loss_rows_bytes": (_sz, [_i, _i]),
-    "ssg_loss_tm_bytes": (_sz, [_i, _i]),
-    "ssg_loss_workspace_layout": (_i, [_i, _i, _i, _i, _i, _i, ctypes.POINTER(ctypes.c_size_t)]),
-    "ssg_filter2d": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
-    "ssg_diffjpeg": (_i, [_vp, _vp, _i, _i, _i, _vp, _f, _vp]),
-    "ssg_usm_scratch_bytes": (_sz, [_i, _i, _i, _i]),
-    "ssg_usm_sharp": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _f, _f, _f, _vp, _sz, _vp]),
-    "ssg_loss_fwd_bwd": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _f, _f, _i, _f, _f, _i, _f, _i, _vp, _vp,
-                              _vp, _vp, _vp, _vp, _sz, _vp, _vp]),
-    "ssg_loss_step": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _f, _f, _i, _f, _f, _i, _f, _i, _vp, _vp,
-                           _vp, _vp, _vp, _vp, _sz, _vp, _vp]),
-    "ssg_augment_crop": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
-    "ssg_pool_swap": (_i, [_vp, _vp, _sz, _vp, _i, _vp]),
-    "ssg_resize": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, ctypes.c_double, ctypes.c_double, _vp]),
-    "ssg_clamp_round": (_i, [_vp, _vp, _sz, _i, _i, _vp]),
-    "ssg_gaussian_noise": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
-    "ssg_poisson_scratch_bytes": (_sz, [_i]),
-    "ssg_poisson_rates": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
-    "ssg_poisson_noise": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
-    "ssg_synth_kernels": (_i, [_vp, _i, _i, _vp, _vp, _vp]),
-    "ssg_kernel_name": (ctypes.c_char_p, [_i, _i, _i]),
-    "ssg_ldl_workspace_bytes": (_sz, [_i, _i, _i]),
-    "ssg_artifact_map": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _sz, _vp]),
-    "ssg_artifact_map_backward": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _sz, _vp]),
-    "ssg_ldl_loss": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _f, _i, _vp, _vp, _vp, _sz, _vp]),
-    "ssg_local_variance": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
-    "ssg_bbl_workspace_bytes": (_sz, [_i, _i, _i, _i, _i, _i]),
-    "ssg_bbl_search": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _f, _f, _vp, _vp, _vp, _vp, _sz, _vp]),
-    "ssg_bbl_loss": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _f, _f, _f, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
-    "ssg_flat_mask": (_i, [_vp, _i, _i, _i, _i, _f, _vp, _vp]),
-    "ssg_bp_workspace_bytes": (_sz, [_i, _i, _i, _i]),
-    "ssg_bp_downsample": (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),
-    "ssg_bp_downsample_backward": (_i, [_vp, _i, _i, _i, _i, _vp, _vp]),
-    "ssg_bp_loss": (_i, [_vp, _vp, _i, _i, _i, _i, _f, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
-    "ssg_metric_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
-    "ssg_psnr_ssim": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _sz, _vp]),
-    "ssg_metric_planes": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
-    "ssg_niqe_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
-    "ssg_niqe": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _sz, _vp]),
-    "ssg_niqe_planes": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
-    "ssg_niqe_features": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _sz, _vp]),
-    "ssg_niqe_table": (_i, [_vp]),
-    "ssg_wavelet_blur": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp]),
-    "ssg_wavelet_decompose": (_i, [_vp, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
-    "ssg_colorfix_wavelet": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _vp]),
-    "ssg_colorfix_workspace_bytes": (_sz, [_i, _i, _i, _i]),
-    "ssg_colorfix_stats": (_i, [_vp, _vp, _i, _i, _i, _i, ctypes.c_double, _vp, _vp, _sz, _vp]),
-    "ssg_colorfix_adain": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),
-    "ssg_ssim_workspace_bytes": (_sz, [_i, _i, _i, _i]),
-    "ssg_ssim_grid_cap": (_i, []),
-    "ssg_ssim_taps": (_i, [_i, _vp]),
-    "ssg_ssim_loss": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp, _sz, _vp]),
-    "ssg_resample_ksize": (_i, [_i, _i, _i]),
-    "ssg_resample_table": (_i, [_i, _i, _i, _vp, _vp]),
-    "ssg_resample_tile": (_i, [_vp, _vp]),
-    "ssg_resample_max_ratio": (_i, []),
-    "ssg_resample": (_i, [_vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp]),
-    "ssg_imresize_out_size": (_i, [_i, ctypes.c_double]),
-    "ssg_imresize_taps": (_i, [ctypes.c_double, _i]),
-    "ssg_imresize_table": (_i, [_i, _i, ctypes.c_double, _i, _vp, _vp]),
-    "ssg_imresize_tiles": (_i, [ctypes.c_double, _i, _vp, _i, _vp]),
-    "ssg_imresize": (_i, [_vp, _i, _i, _i, _i, _i, ctypes.c_double, _i, _vp, _vp, _vp, _vp, _i, _vp, _vp]),
-    "ssg_jpeg_roundtrip_workspace_bytes": (_sz, [_i, _i, _i, _i]),
-    "ssg_jpeg_unit_table": (_i, [_vp]),
-    "ssg_jpeg_roundtrip": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, _i, _i, _vp, _sz, _vp]),
-    # include/similarity.h: the reference operator's own (void, stream-less) interface
-    "ssg_ref_compute_similarity": (None, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i]),
-    "ssg_ref_compute_similarity_backward": (None, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i]),
-    "ssg_last_status": (_i, []),
-    "ssg_device_status": (_i, [_vp]),
-    "ssg_set_operator_plan_threshold": (_i, [_i]),
-    "ssg_operator_pool_trim": (_i, []),
-    "ssg_criteria_scratch_bytes": (_sz, []),
-    "ssg_criteria_sums": (_i, [_vp, _vp, _sz, _vp, _vp, _vp]),
-    "ssg_criteria_grad": (_i, [_vp, _vp, _sz, _vp, _vp, _vp]),
-}
-PROF_PROTOTYPES = {"ssg_set_profile_mask": (_i, [_i]), "ssg_prof_occupancy": (_i, [_i]),
-                   "ssg_prof_set_lds_poison": (_i, [_i, ctypes.c_uint])}   # libssg_hip_prof.so only
+
+def _argtype(name, param):
+    """the ctypes type of one parameter, `T name`, `T *name` or `T name[N]`, of the declaration of `name`"""
+    if "*" in param and "(" not in param:
+        return ctypes.c_void_p
+    m = re.fullmatch(r"(?:const )?(\w+) \w+ ?(\[ ?\d* ?\])?", param)
+    if not m or m.group(1) not in _SCALARS:
+        raise TypeError(f"ssl_amd._lib: cannot type parameter {param!r} of {name}")
+    return ctypes.POINTER(_SCALARS[m.group(1)]) if m.group(2) else _SCALARS[m.group(1)]
+
+
+def _declarations(text):
+    """name -> (restype, [argtypes]) of the `ssg_*` functions a comment-free piece of a header declares"""
+    text = re.sub(r"^[ \t]*#.*$", "", text, flags=re.M)                        # the preprocessor's lines
+    text = re.sub(r"\btypedef\b[^;{]*(\{[^}]*\}[^;]*)?;", "", text)              # types, a struct's members included
+    text = re.sub(r'\bextern\s+"C"\s*\{|^\s*\}\s*$', "", text, flags=re.M)     # the linkage block's braces
+    table = {}
+    for stmt in text.split(";"):
+        stmt = " ".join(stmt.split())
+        if not stmt:
+            continue
+        m = re.fullmatch(r"(.*?)\b(\w+) ?\((.*)\)", stmt)
+        if not m:
+            raise TypeError(f"ssl_amd._lib: not a function declaration: {stmt!r}")
+        ret, name, params = m.group(1).strip(), m.group(2), m.group(3).strip()
+        if not name.startswith("ssg_"):
+            continue                                                          # similarity.h's C++-linkage pair: CXX_SYMBOLS
+        if ret not in _RETURNS:
+            raise TypeError(f"ssl_amd._lib: unknown return type {ret!r} of {name}")
+        if name in table:
+            raise TypeError(f"ssl_amd._lib: {name} is declared twice")
+        table[name] = (_RETURNS[ret], [] if params == "void" else [_argtype(name, p.strip()) for p in params.split(",")])
+    return table
+
+
+def read_header(text):
+    """(prototypes, profiling-build prototypes, constants) of a C header in the style of include/ssg_hip.h."""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+    constants = {m.group(1): int(m.group(2).strip("()"))
+                 for m in re.finditer(r"^[ \t]*#[ \t]*define[ \t]+(SSG_\w+)[ \t]+(\(-?\d+\)|-?\d+)[ \t]*$", text, re.M)}
+    prof = r"^[ \t]*#[ \t]*ifdef[ \t]+SSG_PROFILE\b(.*?)^[ \t]*#[ \t]*endif\b"
+    inside = "".join(re.findall(prof, text, flags=re.M | re.S))
+    return _declarations(re.sub(prof, "", text, flags=re.M | re.S)), _declarations(inside), constants
+
+
+PROTOTYPES, PROF_PROTOTYPES, CONSTANTS = {}, {}, {}       # PROF_PROTOTYPES: libssg_hip_prof.so only
+for _path in (HEADER, REF_HEADER):
+    if not os.path.exists(_path):
+        raise RuntimeError(f"{_path} is missing: ssl_amd binds libssg_hip.so from its headers")
+    with open(_path) as _f:
+        for _table, _part in zip((PROTOTYPES, PROF_PROTOTYPES, CONSTANTS), read_header(_f.read())):
+            _table.update(_part)
 # C++-linkage symbols of include/similarity.h (Itanium mangling of the reference's declarations, similarity.h:2-23)
 CXX_SYMBOLS = ("_Z19_compute_similarityPKfPKiPfiiiiii", "_Z28_compute_similarity_backwardPKfS0_PKiPfiiiiii")
 

@@ -19,7 +19,7 @@ from .engine import _launch, _need_gpu, _ptr, _workspace
 __all__ = ["wavelet_blur", "wavelet_decomposition", "wavelet_reconstruction", "calc_mean_std",
            "adaptive_instance_normalization", "adain_color_fix", "wavelet_color_fix", "color_fix"]
 
-OUT_RAW, OUT_UNIT, OUT_UINT8 = 0, 1, 2
+OUT_RAW, OUT_UNIT, OUT_UINT8 = (_lib.CONSTANTS["SSG_COLORFIX_" + k] for k in ("RAW", "UNIT", "U8_NHWC"))
 _OUT = {'raw': OUT_RAW, 'unit': OUT_UNIT, 'uint8': OUT_UINT8}
 _KINDS = ('wavelet', 'adain', 'nofix')
 MAX_LEVELS = 5

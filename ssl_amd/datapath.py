@@ -233,14 +233,16 @@ def _jpeg_call(x, B, H, W, C, quality, in_f32, out_f32):
     if B * H * W * C > 2 ** 31 - 1:
         raise ValueError("ssl_amd: jpeg_roundtrip takes at most 2^31 - 1 elements per call")
     qs = _jpeg_qualities(quality, B)
-    L = _lib.lib()
+    L, K = _lib.lib(), _lib.CONSTANTS
     out = torch.empty((B, C, H, W) if out_f32 else (B, H, W, C), dtype=torch.float32 if out_f32 else torch.uint8,
                       device=x.device)
+    in_layout = K["SSG_JPEG_IN_F32_NCHW" if in_f32 else "SSG_JPEG_IN_U8_HWC"]
+    out_epilogue = K["SSG_JPEG_OUT_F32_NCHW" if out_f32 else "SSG_JPEG_OUT_U8_HWC"]
     nbytes = L.ssg_jpeg_roundtrip_workspace_bytes(B, H, W, C)
     ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=x.device)
     with torch.cuda.device(x.device):
-        _lib.check(L.ssg_jpeg_roundtrip(_ptr(x), _ptr(out), B, H, W, C, qs.ctypes.data, int(in_f32), int(out_f32),
-                                        _ptr(ws), nbytes, _stream()))
+        _lib.check(L.ssg_jpeg_roundtrip(_ptr(x), _ptr(out), B, H, W, C, qs.ctypes.data, in_layout, out_epilogue, _ptr(ws),
+                                        nbytes, _stream()))
     return out
 
 
@@ -513,7 +515,8 @@ def random_add_poisson_noise(img, scale_range, gray_prob, draws, clip=True, roun
 
 
 # ------------------------------------------------------------------ the kernels the chain convolves with ----
-KERNEL_KINDS = {"pulse": 0, "sinc": 1, "gaussian": 2, "generalized": 3, "plateau": 4}      # SSG_KERNEL_* of ssg_hip.h
+KERNEL_KINDS = {name: _lib.CONSTANTS["SSG_KERNEL_" + name.upper()]
+                for name in ("pulse", "sinc", "gaussian", "generalized", "plateau")}
 # one kernel's parameters (ssg_kernel_record): kind a name of KERNEL_KINDS, size K (odd); an isotropic kernel is
 # sig_y = sig_x with theta = 0; fields a kind does not use stay 0
 KernelRecord = namedtuple("KernelRecord", "kind size sig_x sig_y theta beta omega_c", defaults=(0.0,) * 5)

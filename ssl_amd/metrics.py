@@ -27,8 +27,8 @@ from .engine import _launch, _need_gpu, _ptr, _workspace
 __all__ = ["calculate_psnr", "calculate_ssim", "calculate_niqe", "calculate_metric", "psnr_ssim", "niqe",
            "load_niqe_params", "MetricAverager"]
 
-KIND_F32_RGB, KIND_U8_HWC, KIND_U8_CHW = 0, 1, 2
-KIND_F32_PLANE = 3                      # NIQE only: a float32 (B,H,W) plane (input_order 'HW')
+KIND_F32_RGB, KIND_U8_HWC, KIND_U8_CHW = (_lib.CONSTANTS["SSG_METRIC_" + k] for k in ("F32_RGB", "U8_HWC", "U8_CHW"))
+KIND_F32_PLANE = _lib.CONSTANTS["SSG_NIQE_F32_PLANE"]   # NIQE only: a float32 (B,H,W) plane (input_order 'HW')
 NIQE_BLOCK, NIQE_FEATURES = 96, 36
 NIQE_PARAMS_ENV = "SSL_AMD_NIQE_PARAMS"
 NIQE_PARAMS_FILE = "niqe_pris_params.npz"

@@ -25,8 +25,10 @@ from .engine import _launch, _need_gpu, _ptr
 __all__ = ["resize", "load_img", "from_pil", "multiscale", "multiscale_plan", "subimage_grid", "extract_subimages",
            "subimage_name", "FILTERS", "imresize", "imresize_np", "modcrop"]
 
-FILTERS = {'lanczos': 1, 'bilinear': 2, 'bicubic': 3, 'box': 4, 'hamming': 5}      # Pillow's Image.Resampling numbers
-_OUT = {'uint8': 0, 'unit': 1, 'signed': 2}
+_C = _lib.CONSTANTS                      # the numbers of include/ssg_hip.h
+# Pillow's Image.Resampling numbers
+FILTERS = {name: _C["SSG_RESAMPLE_" + name.upper()] for name in ('lanczos', 'bilinear', 'bicubic', 'box', 'hamming')}
+_OUT = {'uint8': _C["SSG_RESAMPLE_U8_HWC"], 'unit': _C["SSG_RESAMPLE_F32_UNIT"], 'signed': _C["SSG_RESAMPLE_F32_SIGNED"]}
 _tables = {}
 
 
@@ -99,12 +101,12 @@ def resize(img, size, resample='lanczos', out='uint8'):
     xb, xk = _device_table(W, w, filt, dev) if W != w else (None, None)
     yb, yk = _device_table(H, h, filt, dev) if H != h else (None, None)
     kind = _OUT[out]
-    if kind == 0:
+    if kind == _OUT['uint8']:
         res = torch.empty((B, h, w, C), dtype=torch.uint8, device=dev)
     else:
         res = torch.empty((B, C, h, w), dtype=torch.float32, device=dev)
     _launch(dev, L.ssg_resample, _ptr(x), B, C, H, W, h, w, filt, _ptr(xb), _ptr(xk), _ptr(yb), _ptr(yk), kind, _ptr(res))
-    if kind == 0:
+    if kind == _OUT['uint8']:
         res = res if img.dim() == 4 else res[0]
         res = res[..., 0] if img.dim() == 2 else res
     return res
@@ -239,17 +241,17 @@ def imresize_host_table(n, scale, antialiasing=True):
     L = _lib.lib()
     s, aa = _imresize_scale(scale), int(bool(antialiasing))
     taps = L.ssg_imresize_taps(s, aa)
-    if taps == -2:
+    if taps == _C["SSG_E_TOOLARGE"]:
         raise NotImplementedError(f"ssl_amd: imresize takes at most 32 taps per output, that is antialiased scales "
                                   f"down to 1 / 8; scale {s} needs {int(np.ceil(4 / s))}")
     m = L.ssg_imresize_out_size(n, s)
-    if m == -2:
+    if m == _C["SSG_E_TOOLARGE"]:
         raise ValueError(f"ssl_amd: imresize of a side of {n} by {s} has 2^31 pixels or more")
     _lib.check(min(taps, m, 0))
     first = np.empty(m, np.int32)
     weights = np.empty((m, taps), np.float64)
     rc = L.ssg_imresize_table(n, m, s, aa, first.ctypes.data, weights.ctypes.data)
-    if rc == -4:
+    if rc == _C["SSG_E_IMAGESMALL"]:
         raise ValueError(f"ssl_amd: imresize by {s} on a side of {n} pixels reaches past one mirror of the image (every "
                          f"tap must lie in [1 - {n}, {2 * n}], as the reference's padding needs); the side is too small")
     _lib.check(rc)
@@ -274,7 +276,7 @@ def _imresize_launch(x, in_kind, B, C, H, W, s, aa, out_kind):
     yf, yw = _imresize_table(H, s, aa, dev)
     xf, xw = _imresize_table(W, s, aa, dev)
     h, w = yf.numel(), xf.numel()
-    if out_kind == 1:
+    if out_kind == _C["SSG_IMRESIZE_U8_HWC"]:
         res = torch.empty((B, h, w, C), dtype=torch.uint8, device=dev)
     else:
         res = torch.empty((B, C, h, w), dtype=torch.float32, device=dev)
@@ -319,7 +321,8 @@ def imresize(img, scale, antialiasing=True, out=None):
         B, H, W, C = x.shape
         if C not in (1, 3):
             raise ValueError(f"ssl_amd: imresize takes 1 ('L') or 3 ('RGB') channels last for bytes, got {C}")
-        in_kind, out_kind = 1, (2 if out == 'unit' else 1)
+        in_kind = _C["SSG_IMRESIZE_IN_U8_HWC"]
+        out_kind = _C["SSG_IMRESIZE_F32_UNIT" if out == 'unit' else "SSG_IMRESIZE_U8_HWC"]
     elif img.is_floating_point():
         if out is not None:
             raise ValueError(f"ssl_amd: imresize out is for uint8 tensors; a float tensor gives float32, got out={out!r}")
@@ -327,7 +330,7 @@ def imresize(img, scale, antialiasing=True, out=None):
             raise ValueError(f"ssl_amd: imresize takes float (H,W), (C,H,W) or (B,C,H,W), got {tuple(img.shape)}")
         x = img.reshape((1,) * (4 - img.dim()) + tuple(img.shape))
         B, C, H, W = x.shape
-        in_kind, out_kind = 0, 0
+        in_kind, out_kind = _C["SSG_IMRESIZE_IN_F32"], _C["SSG_IMRESIZE_F32_PLANES"]
     else:
         raise TypeError(f"ssl_amd: imresize takes floating or uint8 tensors, got {img.dtype}")
     if min(B, C, H, W) < 1:
@@ -336,11 +339,11 @@ def imresize(img, scale, antialiasing=True, out=None):
     if max(B * C * H * W, B * C * h * w) > 2 ** 31 - 1:
         raise ValueError("ssl_amd: imresize takes at most 2^31 - 1 elements per call, input and output")
     _need_gpu(img)
-    x = x.detach().to(torch.float32).contiguous() if in_kind == 0 else x.contiguous()
+    x = x.detach().to(torch.float32).contiguous() if in_kind == _C["SSG_IMRESIZE_IN_F32"] else x.contiguous()
     res = _imresize_launch(x, in_kind, B, C, H, W, s, aa, out_kind)
-    if out_kind == 2:
+    if out_kind == _C["SSG_IMRESIZE_F32_UNIT"]:
         return res
-    if in_kind == 0:
+    if in_kind == _C["SSG_IMRESIZE_IN_F32"]:
         return res.reshape(tuple(img.shape[:-2]) + (h, w))
     res = res if img.dim() == 4 else res[0]
     return res[..., 0] if img.dim() == 2 else res

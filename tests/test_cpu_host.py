@@ -39,8 +39,8 @@ def test_library_builds_loads_and_exports_header_symbols():
     assert demangled[0] == "_compute_similarity(float const*, int const*, float*, int, int, int, int, int, int)"
     assert demangled[1] == ("_compute_similarity_backward(float const*, float const*, int const*, float*, int, int, int, "
                             "int, int, int)")
-    # every prototype the Python binding uses is declared in the header
-    assert set(_lib.PROTOTYPES) <= declared - profile_only
+    # the Python binding's prototypes are the header's declarations, no more and no fewer
+    assert set(_lib.PROTOTYPES) == declared - profile_only
     lib = _lib.lib()
     assert lib.ssg_abi_version() == 6
     assert lib.ssg_status_string(0) == b"ok"
@@ -48,6 +48,80 @@ def test_library_builds_loads_and_exports_header_symbols():
     assert lib.ssg_kernel_name(25, 9, 0).startswith(b"ssg_fwd_")
     assert lib.ssg_kernel_name(7, 3, 1) == b"ssg_bwd_generic"
     assert lib.ssg_loss_workspace_bytes(16, 256, 256, 100000, 25) > 100000 * 12
+
+
+def test_every_declaration_is_bound_with_its_arity():
+    """PROTOTYPES and PROF_PROTOTYPES together hold exactly the functions the two headers declare, each with as many
+    argtypes as its declaration has parameters (counted here, apart from the binding's reader)."""
+    from ssl_amd import _lib
+    hdr = open(_lib.HEADER).read() + open(os.path.join(os.path.dirname(_lib.HEADER), "similarity.h")).read()
+    declared = set(re.findall(r"\b(ssg_[a-z_0-9]+)\s*\(", hdr)) - {"ssg_stream_t"}
+    assert not set(_lib.PROTOTYPES) & set(_lib.PROF_PROTOTYPES)
+    bound = dict(_lib.PROTOTYPES, **_lib.PROF_PROTOTYPES)
+    assert set(bound) == declared
+    code = re.sub(r"/\*.*?\*/", " ", hdr, flags=re.S)
+    for name in sorted(declared):
+        params = re.findall(r"\b" + name + r"\s*\(([^();]*)\)\s*;", code)
+        assert len(params) == 1, name
+        arity = 0 if params[0].strip() == "void" else params[0].count(",") + 1
+        assert len(bound[name][1]) == arity, (name, params[0])
+    i, j = code.index("#ifdef SSG_PROFILE"), code.index("#endif", code.index("#ifdef SSG_PROFILE"))
+    assert set(_lib.PROF_PROTOTYPES) == set(re.findall(r"\b(ssg_[a-z_0-9]+)\s*\(", code[i:j]))
+    assert all(isinstance(v, int) for v in _lib.CONSTANTS.values())
+    assert set(_lib.CONSTANTS) == set(re.findall(r"^#define (SSG_\w+)[ \t]+[(\-\d]", code, re.M))
+
+
+_SMALL_HEADER = """
+#ifndef SSG_SMALL_H
+#define SSG_SMALL_H
+typedef void *ssg_stream_t; /* hipStream_t */
+#define SSG_X (-4)   /* a status */
+#define SSG_Y 3 /* note */
+#define SSG_NOT_A_NUMBER "text"
+typedef struct ssg_rec {
+  int32_t kind;   /* SSG_KIND_* */
+  double sig_x, sig_y;
+} ssg_rec;   /* 24 bytes */
+int ssg_three(const float *img, int B,
+              float *out /* nullable, 2 floats */,   // and a line comment, with a comma
+              ssg_stream_t stream);
+int ssg_none(void);
+const char *ssg_text(int status);
+void ssg_quiet(const ssg_rec *records, double scale, unsigned pattern, size_t n);
+size_t ssg_layout(int fused, size_t out[9], float taps[]);
+#ifdef SSG_PROFILE
+/* profiling build only */
+int ssg_prof_only(unsigned long long *host, int n);
+#endif
+const char *ssg_after(int ks);
+#endif
+"""
+
+
+def test_header_reader_on_small_headers():
+    """ssl_amd._lib.read_header on header texts written here: comments, line breaks, (void), arrays, the typedef, the
+    profiling block and the constants -- and a refusal, by name, of whatever it cannot type."""
+    from ssl_amd._lib import read_header
+    i, f, d, sz, vp, u = (ctypes.c_int, ctypes.c_float, ctypes.c_double, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_uint)
+    protos, prof, consts = read_header(_SMALL_HEADER)
+    assert protos == {"ssg_three": (i, [vp, i, vp, vp]), "ssg_none": (i, []), "ssg_text": (ctypes.c_char_p, [i]),
+                      "ssg_quiet": (None, [vp, d, u, sz]),
+                      "ssg_layout": (sz, [i, ctypes.POINTER(sz), ctypes.POINTER(f)]), "ssg_after": (ctypes.c_char_p, [i])}
+    assert prof == {"ssg_prof_only": (i, [vp, i])}
+    assert consts == {"SSG_X": -4, "SSG_Y": 3}
+    assert read_header("void _compute(const float *image, const int mc);\nint ssg_last(void);")[0] == {"ssg_last": (i, [])}
+    for bad in ("int ssg_bad(int n, long count);",                   # a scalar the table does not name
+                "int ssg_bad(ssg_rec by_value);",                    # a struct passed by value
+                "int ssg_bad(void (*callback)(int), int n);",        # a function pointer
+                "int ssg_bad(int);",                                 # a parameter without a name
+                "long ssg_bad(int n);", "float *ssg_bad(int n);",    # return types the table does not name
+                "int ssg_bad(int n);\nint ssg_bad(int n);"):         # declared twice
+        with pytest.raises(TypeError, match="ssg_bad"):
+            read_header(bad)
+    with pytest.raises(TypeError, match="ssg_prof_bad"):
+        read_header("#ifdef SSG_PROFILE\nint ssg_prof_bad(short n);\n#endif\n")
+    with pytest.raises(TypeError, match="not a function declaration"):
+        read_header("int ssg_global_variable;")
 
 
 def test_product_library_has_no_profiling_switch():

@@ -1,12 +1,10 @@
 """Profiling build: start / end clock and CU of every ssg_fwd_strip workgroup of one fused C5 step."""
-import ctypes, os, sys
+import os, sys
 import numpy as np, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from ssl_amd import _lib, engine, synth
 dev = torch.device("cuda:0")
 with _lib.profile_build() as L:
-    L.ssg_prof_strip_times.restype = ctypes.c_int
-    L.ssg_prof_strip_times.argtypes = [ctypes.c_void_p, ctypes.c_int]
     H = W = 512
     gt = synth.natural_like(300, H, W)[None]; sr = synth.degrade(gt[0], 7)[None]; m = np.ones((1, 1, H, W), np.float32)
     step = engine.LossStep(1, 3, H, W, 49, 13, 1.0, 1e-10, True, 1e3, 1e3, device=dev, capacity=H * W + 64, materialise=False)
