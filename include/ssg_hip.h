@@ -70,6 +70,7 @@ typedef void *ssg_stream_t; /* hipStream_t */
 /* 6, additive: + ssg_imresize, ssg_imresize_out_size / _taps / _table / _tiles (MATLAB's bicubic imresize, section (O)). */
 /* 6, additive: + ssg_jpeg_roundtrip, ssg_jpeg_roundtrip_workspace_bytes, ssg_jpeg_unit_table (libjpeg's baseline round
  * trip, section (P)); nothing existing changed, so the version number stays. */
+/* 6, additive: + ssg_gan_sums, ssg_gan_grad, ssg_gan_workspace_bytes, ssg_gan_grid_cap (the GAN criteria, section (Q)). */
 int ssg_abi_version(void);
 const char *ssg_status_string(int status);
 /* Device-side refusals that no return value can carry (everything is asynchronous): waits for `stream`, then returns
@@ -884,6 +885,47 @@ size_t ssg_jpeg_roundtrip_workspace_bytes(int B, int H, int W, int channels);
 int ssg_jpeg_unit_table(float *table /* 256 floats, host */);
 int ssg_jpeg_roundtrip(const void *in, void *out, int B, int H, int W, int channels, const int *qualities,
                        int in_layout, int out_epilogue, void *workspace, size_t workspace_bytes, ssg_stream_t stream);
+
+/* ---------------------------------------------------------------- (Q) ----
+ * The GAN criteria, plain and relativistic (basicsr/losses/gan_loss.py:11-140 GANLoss / MultiScaleGANLoss; KAIR's
+ * train_BSGRAN/models/loss.py:135-172 GANLoss; the relativistic-average lines cri_gan(real - torch.mean(fake), ...) of
+ * the nine basicsr/models/ *ssl_model.py files and of KAIR's model_ssl.py), ssl_amd/csrc/ssg_gan.hip.  x fp32, n >= 1
+ * elements; the criteria are means over every element, so no shape is taken.  Per element d = x - shift[0] in fp32 with
+ * one rounding (shift: one float ON THE DEVICE, the mean of the other tensor of a relativistic call; NULL: d = x), and
+ * with t = label, s = sign (+1 or -1; it is checked for every kind and used by the last three):
+ *   SSG_GAN_BCE       l = max(d, 0) - d t + log1p(exp(-|d|))      l' = sigmoid(d) - t      vanilla; KAIR gan, ragan
+ *   SSG_GAN_LS        l = (d - t)^2                                l' = 2 (d - t)           lsgan
+ *   SSG_GAN_LINEAR    l = s d                                      l' = s                   wgan, the hinge generator
+ *                                                                                           term, plain sums (s = 1)
+ *   SSG_GAN_SOFTPLUS  l = softplus(s d)                            l' = s sigmoid(s d)      wgan_softplus, softplusgan
+ *   SSG_GAN_HINGE     l = relu(1 + s d)                            l' = s where 1 + s d > 0 (or NaN), else 0: exactly
+ *                                                                       0 at 1 + s d = 0, as torch's ReLU gives it
+ * Every operation is fp32, rounded once, in overflow-safe form (d = +-100 gives 100 or 0, never inf or NaN); a NaN
+ * element is never dropped by a max: it reaches the sum.
+ * ssg_gan_sums: sums_out[0] = sum of l(d_i), sums_out[1] = sum of l'(d_i): TWO DOUBLES on the device, the fp32 element
+ *   values added in fp64 in a fixed order (one partial pair per workgroup in `workspace`, at most ssg_gan_grid_cap()
+ *   workgroups of 256 threads and four elements per thread and trip, then one folding workgroup; a call of a single
+ *   workgroup, n <= 1024, writes sums_out itself and is one launch).  No atomics: the same bits from call to call.  The
+ *   mean of a tensor is SSG_GAN_LINEAR with s = 1 over n; sum l' is what the path through a relativistic mean needs.
+ * ssg_gan_grad: grad[i] = (float)(coef[0] * l'(d_i) + coef[1]), coef TWO DOUBLES on the device: coef[0] carries
+ *   upstream x weight / n, coef[1] the constant that flows back through a mean (0 without one).  One launch.
+ * Loads and stores are 16 bytes wide behind a scalar head and in front of a scalar tail: x and grad need only a
+ * float's own alignment.  No allocation, synchronisation or host read.
+ * ssg_gan_workspace_bytes: 16 bytes per workgroup of the cap (16,384), whatever n.
+ * Status, decided before any launch with the outputs untouched: SSG_E_BADARG for a null pointer (shift excepted), n = 0,
+ * a kind outside 0 .. 4 or a sign other than +1 or -1; SSG_E_ALIGN for an x or grad that is not 4-byte aligned or a
+ * workspace, sums_out or coef that is not 8-byte aligned. */
+#define SSG_GAN_BCE 0
+#define SSG_GAN_LS 1
+#define SSG_GAN_LINEAR 2
+#define SSG_GAN_SOFTPLUS 3
+#define SSG_GAN_HINGE 4
+size_t ssg_gan_workspace_bytes(void);
+int ssg_gan_grid_cap(void);
+int ssg_gan_sums(const float *x, size_t n, int kind, float sign, float label, const float *shift /* nullable */,
+                 void *workspace, double *sums_out, ssg_stream_t stream);
+int ssg_gan_grad(const float *x, size_t n, int kind, float sign, float label, const float *shift /* nullable */,
+                 const double *coef, float *grad, ssg_stream_t stream);
 
 #ifdef SSG_PROFILE
 /* PROFILING BUILD ONLY (libssg_hip_prof.so, compiled with -DSSG_PROFILE; the product library libssg_hip.so does not

@@ -1480,6 +1480,20 @@ int ssg_ssim_loss(const float *x, const float *y, int B, int C, int H, int W, in
                           (hipStream_t)stream);
 }
 
+size_t ssg_gan_workspace_bytes(void) { return gan_workspace_bytes(); }
+
+int ssg_gan_grid_cap(void) { return gan_grid_cap(); }
+
+int ssg_gan_sums(const float *x, size_t n, int kind, float sign, float label, const float *shift, void *workspace,
+                 double *sums_out, ssg_stream_t stream) {
+  return launch_gan_sums(x, n, kind, sign, label, shift, workspace, sums_out, (hipStream_t)stream);
+}
+
+int ssg_gan_grad(const float *x, size_t n, int kind, float sign, float label, const float *shift, const double *coef,
+                 float *grad, ssg_stream_t stream) {
+  return launch_gan_grad(x, n, kind, sign, label, shift, coef, grad, (hipStream_t)stream);
+}
+
 int ssg_device_status(ssg_stream_t stream) {
   int *w = device_status_word();
   if (!w) return 0;

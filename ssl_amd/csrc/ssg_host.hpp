@@ -120,6 +120,14 @@ size_t ssim_workspace_bytes(int B, int C, int H, int W);
 int launch_ssim_loss(const float *x, const float *y, int B, int C, int H, int W, int window_size, float *grad_x,
                      double *sums_out, void *workspace, size_t workspace_bytes, hipStream_t st);
 
+// ---- ssg_gan.hip: the GAN criteria, plain and relativistic: sum l and sum l' in one pass, the gradient in one ----
+int gan_grid_cap();
+size_t gan_workspace_bytes();
+int launch_gan_sums(const float *x, size_t n, int kind, float sign, float label, const float *shift, void *workspace,
+                    double *sums_out, hipStream_t st);
+int launch_gan_grad(const float *x, size_t n, int kind, float sign, float label, const float *shift, const double *coef,
+                    float *grad, hipStream_t st);
+
 // ---- ssg_resample.hip: Pillow's 8-bit convolution resize (entry points beside its kernel) ----
 int resample_ksize(int in, int out, int filter);                                   // host only
 int resample_table(int in, int out, int filter, int *bounds, int *coef);           // host only: fp64, libm's sin / cos

@@ -3,3 +3,4 @@ from .loss_util import get_artifact_map, get_local_weights, get_refined_artifact
 from .lazy import LazySSG, lazy_enabled, set_lazy  # noqa: F401
 from .bebygan import BBL, BackProjectionLoss, BestBuddyLoss, get_flat_mask, imresize  # noqa: F401
 from .ssim import SSIMLoss, create_window, gaussian, ssim  # noqa: F401
+from .gan_loss import GANLoss, MultiScaleGANLoss  # noqa: F401
