@@ -71,6 +71,9 @@ typedef void *ssg_stream_t; /* hipStream_t */
 /* 6, additive: + ssg_jpeg_roundtrip, ssg_jpeg_roundtrip_workspace_bytes, ssg_jpeg_unit_table (libjpeg's baseline round
  * trip, section (P)); nothing existing changed, so the version number stays. */
 /* 6, additive: + ssg_gan_sums, ssg_gan_grad, ssg_gan_workspace_bytes, ssg_gan_grid_cap (the GAN criteria, section (Q)). */
+/* 6, additive: + ssg_spsr_map, ssg_spsr_map_backward, ssg_spsr_loss, ssg_spsr_loss_backward, ssg_spsr_branch_loss,
+ * ssg_spsr_branch_grad, ssg_pixel_sums, ssg_pixel_grad, ssg_spsr_workspace_bytes, ssg_spsr_grid_cap (SPSR's gradient map
+ * and the pixel criteria, section (R)). */
 int ssg_abi_version(void);
 const char *ssg_status_string(int status);
 /* Device-side refusals that no return value can carry (everything is asynchronous): waits for `stream`, then returns
@@ -926,6 +929,62 @@ int ssg_gan_sums(const float *x, size_t n, int kind, float sign, float label, co
                  void *workspace, double *sums_out, ssg_stream_t stream);
 int ssg_gan_grad(const float *x, size_t n, int kind, float sign, float label, const float *shift /* nullable */,
                  const double *coef, float *grad, ssg_stream_t stream);
+
+/* ---------------------------------------------------------------- (R) ----
+ * SPSR's gradient map and the pixel criteria on it (basicsr/models/spsrssl_model.py:18-84 Get_gradient and
+ * Get_gradient_nopadding, which are the same arithmetic; :363 cri_pix_gradSR(G(output), G(gt)); :368
+ * cri_pix_gradBranch(branch, G(gt)); basicsr/losses/basic_loss.py:69-128 MSELoss, CharbonnierLoss),
+ * ssl_amd/csrc/ssg_spsr.hip.  fp32 NCHW contiguous; a batch is planes = B C independent H x W planes, planes, H, W >= 1,
+ * planes H W < 2^31.  Every operation is fp32 and rounded on its own (no fused multiply-add):
+ *   map       v = x[i+1,j] - x[i-1,j], h = x[i,j+1] - x[i,j-1], a neighbour outside the plane is 0 (never read: with
+ *             H = 1 or W = 1 that difference is 0), m = sqrtf((v v + h h) + 1e-6f).
+ *   adjoint   dx[i,j] = ((a[i-1,j] - a[i+1,j]) + b[i,j-1]) - b[i,j+1], a = (w v) / m, b = (w h) / m recomputed from x
+ *             at the neighbour (terms outside the plane are 0), w the gradient that arrives at the map value.
+ *   criteria  d = p - q;  SSG_PIX_L1 |d|, l' = sign(d) with sign(0) = 0;  SSG_PIX_MSE d d, l' = 2 d;
+ *             SSG_PIX_CHARBONNIER sqrtf(d d + eps), l' = d / sqrtf(d d + eps).  eps is read by the last only but is
+ *             checked for every kind.
+ * ssg_spsr_map: map = G(x).  One launch.
+ * ssg_spsr_map_backward: grad_x = the adjoint with w = grad_map; x is all the state.  One launch.
+ * ssg_spsr_loss: sum_out[0] = sum of crit(G(x) - G(target)), ONE DOUBLE on the device, neither map stored -- unless
+ *   map_out is given, which receives G(x), the same bits as ssg_spsr_map's.  The fp32 element values are added in fp64 in
+ *   a fixed order: one partial per workgroup in `workspace`, at most ssg_spsr_grid_cap() workgroups of 256 threads, four
+ *   elements per thread and trip, then one folding workgroup (a call of a single workgroup, planes H W <= 1024, writes
+ *   sum_out itself).  No atomics: the same bits from call to call.
+ * ssg_spsr_loss_backward: grad_x = the adjoint with w = (float)(coef[0] crit'(m_x - m_target)) + grad_map: coef ONE
+ *   DOUBLE on the device (upstream x weight / n), grad_map the nullable upstream gradient of the emitted map.  One
+ *   launch serves the loss and whatever else consumed the map.  No gradient for the target.
+ * ssg_spsr_branch_loss / _grad: sum_out[0] = sum of crit(branch - G(gt)) with G(gt) formed on the fly, and
+ *   grad_branch[i] = (float)(coef[0] crit'(branch_i - G(gt)_i)); element-wise streams.
+ * ssg_pixel_sums / _grad: the same two for two flat tensors of n >= 1 elements, sum of crit(pred - target) and
+ *   (float)(coef[0] crit'(pred_i - target_i)): MSELoss and CharbonnierLoss (and L1).
+ * Accesses are 16 bytes wide behind a scalar head and in front of a scalar tail wherever the tensors share the first
+ * one's alignment; every tensor needs only a float's own alignment and W need not be a multiple of 4.  Plane p of a
+ * batch is the same bits as the plane computed alone.  No allocation, synchronisation or host read.
+ * ssg_spsr_workspace_bytes: 8 bytes per workgroup of the cap, whatever the shape.
+ * Status, decided before any launch with the outputs untouched: SSG_E_BADARG for a null pointer (map_out and grad_map
+ * of the two loss calls excepted), planes, H, W or n < 1, planes H W >= 2^31, a kind outside 0 .. 2, an eps that is
+ * negative or not finite; SSG_E_ALIGN for a float pointer that is not 4-byte aligned or a workspace, sum_out or coef
+ * that is not 8-byte aligned. */
+#define SSG_PIX_L1 0
+#define SSG_PIX_MSE 1
+#define SSG_PIX_CHARBONNIER 2
+size_t ssg_spsr_workspace_bytes(void);
+int ssg_spsr_grid_cap(void);
+int ssg_spsr_map(const float *x, int planes, int H, int W, float *map, ssg_stream_t stream);
+int ssg_spsr_map_backward(const float *x, const float *grad_map, int planes, int H, int W, float *grad_x,
+                          ssg_stream_t stream);
+int ssg_spsr_loss(const float *x, const float *target, int planes, int H, int W, int kind, float eps,
+                  float *map_out /* nullable */, void *workspace, double *sum_out, ssg_stream_t stream);
+int ssg_spsr_loss_backward(const float *x, const float *target, const float *grad_map /* nullable */, const double *coef,
+                           int planes, int H, int W, int kind, float eps, float *grad_x, ssg_stream_t stream);
+int ssg_spsr_branch_loss(const float *branch, const float *gt, int planes, int H, int W, int kind, float eps,
+                         void *workspace, double *sum_out, ssg_stream_t stream);
+int ssg_spsr_branch_grad(const float *branch, const float *gt, int planes, int H, int W, int kind, float eps,
+                         const double *coef, float *grad_branch, ssg_stream_t stream);
+int ssg_pixel_sums(const float *pred, const float *target, size_t n, int kind, float eps, void *workspace,
+                   double *sum_out, ssg_stream_t stream);
+int ssg_pixel_grad(const float *pred, const float *target, size_t n, int kind, float eps, const double *coef,
+                   float *grad_pred, ssg_stream_t stream);
 
 #ifdef SSG_PROFILE
 /* PROFILING BUILD ONLY (libssg_hip_prof.so, compiled with -DSSG_PROFILE; the product library libssg_hip.so does not

@@ -1494,6 +1494,98 @@ int ssg_gan_grad(const float *x, size_t n, int kind, float sign, float label, co
   return launch_gan_grad(x, n, kind, sign, label, shift, coef, grad, (hipStream_t)stream);
 }
 
+// ---- (R) SPSR's gradient map and the pixel criteria: every refusal is decided here, before any launch ----
+static bool spsr_unaligned(const void *p, size_t a) { return p && (size_t)p % a; }
+
+static int spsr_check_planes(int planes, int H, int W) {
+  if (planes < 1 || H < 1 || W < 1) return SSG_E_BADARG;
+  return (unsigned long long)planes * (unsigned long long)H * (unsigned long long)W >= (1ull << 31) ? SSG_E_BADARG : 0;
+}
+
+static int spsr_check_kind(int kind, float eps) {
+  if (kind < SSG_PIX_L1 || kind > SSG_PIX_CHARBONNIER) return SSG_E_BADARG;
+  return eps >= 0.f && eps <= 3.402823466e38f ? 0 : SSG_E_BADARG;   // (a NaN fails both comparisons)
+}
+
+size_t ssg_spsr_workspace_bytes(void) { return spsr_workspace_bytes(); }
+
+int ssg_spsr_grid_cap(void) { return spsr_grid_cap(); }
+
+int ssg_spsr_map(const float *x, int planes, int H, int W, float *map, ssg_stream_t stream) {
+  if (!x || !map) return SSG_E_BADARG;
+  if (const int rc = spsr_check_planes(planes, H, W)) return rc;
+  if (spsr_unaligned(x, 4) || spsr_unaligned(map, 4)) return SSG_E_ALIGN;
+  return launch_spsr_map(x, planes, H, W, map, (hipStream_t)stream);
+}
+
+int ssg_spsr_map_backward(const float *x, const float *grad_map, int planes, int H, int W, float *grad_x,
+                          ssg_stream_t stream) {
+  if (!x || !grad_map || !grad_x) return SSG_E_BADARG;
+  if (const int rc = spsr_check_planes(planes, H, W)) return rc;
+  if (spsr_unaligned(x, 4) || spsr_unaligned(grad_map, 4) || spsr_unaligned(grad_x, 4)) return SSG_E_ALIGN;
+  return launch_spsr_gather(x, nullptr, grad_map, nullptr, planes, H, W, SSG_PIX_L1, 0.f, grad_x, (hipStream_t)stream);
+}
+
+int ssg_spsr_loss(const float *x, const float *target, int planes, int H, int W, int kind, float eps, float *map_out,
+                  void *workspace, double *sum_out, ssg_stream_t stream) {
+  if (!x || !target || !workspace || !sum_out) return SSG_E_BADARG;
+  if (const int rc = spsr_check_planes(planes, H, W)) return rc;
+  if (const int rc = spsr_check_kind(kind, eps)) return rc;
+  if (spsr_unaligned(x, 4) || spsr_unaligned(target, 4) || spsr_unaligned(map_out, 4) || spsr_unaligned(workspace, 8) ||
+      spsr_unaligned(sum_out, 8))
+    return SSG_E_ALIGN;
+  return launch_spsr_loss(x, target, planes, H, W, kind, eps, map_out, workspace, sum_out, (hipStream_t)stream);
+}
+
+int ssg_spsr_loss_backward(const float *x, const float *target, const float *grad_map, const double *coef, int planes,
+                           int H, int W, int kind, float eps, float *grad_x, ssg_stream_t stream) {
+  if (!x || !target || !coef || !grad_x) return SSG_E_BADARG;
+  if (const int rc = spsr_check_planes(planes, H, W)) return rc;
+  if (const int rc = spsr_check_kind(kind, eps)) return rc;
+  if (spsr_unaligned(x, 4) || spsr_unaligned(target, 4) || spsr_unaligned(grad_map, 4) || spsr_unaligned(grad_x, 4) ||
+      spsr_unaligned(coef, 8))
+    return SSG_E_ALIGN;
+  return launch_spsr_gather(x, target, grad_map, coef, planes, H, W, kind, eps, grad_x, (hipStream_t)stream);
+}
+
+int ssg_spsr_branch_loss(const float *branch, const float *gt, int planes, int H, int W, int kind, float eps,
+                         void *workspace, double *sum_out, ssg_stream_t stream) {
+  if (!branch || !gt || !workspace || !sum_out) return SSG_E_BADARG;
+  if (const int rc = spsr_check_planes(planes, H, W)) return rc;
+  if (const int rc = spsr_check_kind(kind, eps)) return rc;
+  if (spsr_unaligned(branch, 4) || spsr_unaligned(gt, 4) || spsr_unaligned(workspace, 8) || spsr_unaligned(sum_out, 8))
+    return SSG_E_ALIGN;
+  return launch_spsr_branch_sums(branch, gt, planes, H, W, kind, eps, workspace, sum_out, (hipStream_t)stream);
+}
+
+int ssg_spsr_branch_grad(const float *branch, const float *gt, int planes, int H, int W, int kind, float eps,
+                         const double *coef, float *grad_branch, ssg_stream_t stream) {
+  if (!branch || !gt || !coef || !grad_branch) return SSG_E_BADARG;
+  if (const int rc = spsr_check_planes(planes, H, W)) return rc;
+  if (const int rc = spsr_check_kind(kind, eps)) return rc;
+  if (spsr_unaligned(branch, 4) || spsr_unaligned(gt, 4) || spsr_unaligned(grad_branch, 4) || spsr_unaligned(coef, 8))
+    return SSG_E_ALIGN;
+  return launch_spsr_branch_grad(branch, gt, planes, H, W, kind, eps, coef, grad_branch, (hipStream_t)stream);
+}
+
+int ssg_pixel_sums(const float *pred, const float *target, size_t n, int kind, float eps, void *workspace,
+                   double *sum_out, ssg_stream_t stream) {
+  if (!pred || !target || !workspace || !sum_out || n < 1) return SSG_E_BADARG;
+  if (const int rc = spsr_check_kind(kind, eps)) return rc;
+  if (spsr_unaligned(pred, 4) || spsr_unaligned(target, 4) || spsr_unaligned(workspace, 8) || spsr_unaligned(sum_out, 8))
+    return SSG_E_ALIGN;
+  return launch_pixel_sums(pred, target, n, kind, eps, workspace, sum_out, (hipStream_t)stream);
+}
+
+int ssg_pixel_grad(const float *pred, const float *target, size_t n, int kind, float eps, const double *coef,
+                   float *grad_pred, ssg_stream_t stream) {
+  if (!pred || !target || !coef || !grad_pred || n < 1) return SSG_E_BADARG;
+  if (const int rc = spsr_check_kind(kind, eps)) return rc;
+  if (spsr_unaligned(pred, 4) || spsr_unaligned(target, 4) || spsr_unaligned(grad_pred, 4) || spsr_unaligned(coef, 8))
+    return SSG_E_ALIGN;
+  return launch_pixel_grad(pred, target, n, kind, eps, coef, grad_pred, (hipStream_t)stream);
+}
+
 int ssg_device_status(ssg_stream_t stream) {
   int *w = device_status_word();
   if (!w) return 0;

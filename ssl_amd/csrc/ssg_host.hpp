@@ -128,6 +128,24 @@ int launch_gan_sums(const float *x, size_t n, int kind, float sign, float label,
 int launch_gan_grad(const float *x, size_t n, int kind, float sign, float label, const float *shift, const double *coef,
                     float *grad, hipStream_t st);
 
+// ---- ssg_spsr.hip: SPSR's gradient map, its adjoint, the criteria fused on it, the streaming pixel criteria ----
+int spsr_grid_cap();
+size_t spsr_workspace_bytes();
+int launch_spsr_map(const float *x, int planes, int H, int W, float *map, hipStream_t st);
+int launch_spsr_loss(const float *x, const float *t, int planes, int H, int W, int kind, float eps, float *map_out,
+                     void *workspace, double *sum_out, hipStream_t st);
+// t == nullptr: the map's own adjoint of gmap; else the fused loss's, coef[0] crit' (+ gmap where given)
+int launch_spsr_gather(const float *x, const float *t, const float *gmap, const double *coef, int planes, int H, int W,
+                       int kind, float eps, float *dx, hipStream_t st);
+int launch_spsr_branch_sums(const float *branch, const float *gt, int planes, int H, int W, int kind, float eps,
+                            void *workspace, double *sum_out, hipStream_t st);
+int launch_spsr_branch_grad(const float *branch, const float *gt, int planes, int H, int W, int kind, float eps,
+                            const double *coef, float *grad, hipStream_t st);
+int launch_pixel_sums(const float *a, const float *b, size_t n, int kind, float eps, void *workspace, double *sum_out,
+                      hipStream_t st);
+int launch_pixel_grad(const float *a, const float *b, size_t n, int kind, float eps, const double *coef, float *grad,
+                      hipStream_t st);
+
 // ---- ssg_resample.hip: Pillow's 8-bit convolution resize (entry points beside its kernel) ----
 int resample_ksize(int in, int out, int filter);                                   // host only
 int resample_table(int in, int out, int filter, int *bounds, int *coef);           // host only: fp64, libm's sin / cos

@@ -853,3 +853,190 @@ def check_ssim_window(window_size):
     if window_size > SSIM_MAX_WINDOW:
         raise ValueError(f"ssl_amd: SSIM runs odd window sizes up to {SSIM_MAX_WINDOW} only, got {window_size}")
     return window_size
+
+
+# ----------------------------------- SPSR's gradient map and the pixel criteria on it (ssg_spsr.hip, section (R)) ----
+PIXEL_KINDS = {name: _lib.CONSTANTS["SSG_PIX_" + name.upper()] for name in ("l1", "mse", "charbonnier")}
+
+
+def _pixel_kind(kind, eps):
+    if kind not in PIXEL_KINDS:
+        raise ValueError(f"ssl_amd: criterion must be one of {sorted(PIXEL_KINDS)}, got {kind!r}")
+    eps = float(eps)
+    if not 0.0 <= eps < float("inf"):
+        raise ValueError(f"ssl_amd: eps must be finite and not negative, got {eps!r}")
+    return PIXEL_KINDS[kind], eps
+
+
+def _planes(name, x, *same):
+    """(planes, H, W) of the (B,C,H,W) tensor x after the checks every entry point of the family makes."""
+    _need_gpu(x, *same)
+    if x.dim() != 4 or x.numel() == 0 or any(t.shape != x.shape for t in same):
+        raise ValueError(f"ssl_amd: {name} takes non-empty (B,C,H,W) tensors of one shape, got "
+                         + ", ".join(str(tuple(t.shape)) for t in (x,) + same))
+    if not all(t.dtype.is_floating_point for t in (x,) + same):
+        raise ValueError(f"ssl_amd: {name} takes floating tensors, got " + ", ".join(str(t.dtype) for t in (x,) + same))
+    if x.numel() >= 2 ** 31:
+        raise ValueError(f"ssl_amd: {name} indexes a call's elements in 31 bits, got {x.numel()}")
+    return x.shape[0] * x.shape[1], x.shape[2], x.shape[3]
+
+
+def _no_target_grad(name, t):
+    if t.requires_grad:
+        raise ValueError(f"ssl_amd: {name} is differentiable with respect to its first tensor only, but the target "
+                         "requires grad; detach it")
+
+
+def _sum_call(dev, fn, *args):
+    """One of the family's sums entry points: (..., workspace, sum_out, stream) -> the fp64 sum, (1,) on the device."""
+    total = torch.empty(1, dtype=torch.float64, device=dev)
+    ws, _ = _workspace(_lib.lib().ssg_spsr_workspace_bytes(), dev)
+    _launch(dev, fn, *args, _ptr(ws), _ptr(total))
+    return total
+
+
+def _coef(g, scale, dev):
+    """The device double a gradient pass multiplies crit' by: upstream x weight / n (0 where nothing flows in)."""
+    if g is None:
+        return torch.zeros(1, dtype=torch.float64, device=dev)
+    return g.detach().to(torch.float64).reshape(1) * scale
+
+
+class _GradientMapFn(torch.autograd.Function):
+    """m = sqrt(v^2 + h^2 + 1e-6) per plane (spsrssl_model.py:18-84): one ssg_spsr_map launch; backward one
+    ssg_spsr_map_backward launch from x alone."""
+
+    @staticmethod
+    def forward(ctx, x):
+        planes, H, W = _planes("gradient_map", x)
+        a = _f32c(x)
+        m = torch.empty_like(a)
+        _launch(a.device, _lib.lib().ssg_spsr_map, _ptr(a), planes, H, W, _ptr(m))
+        if ctx.needs_input_grad[0]:
+            ctx.save_for_backward(a)
+        ctx.in_dtype = x.dtype
+        return m.to(x.dtype)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_map):
+        a, = ctx.saved_tensors
+        B, C, H, W = a.shape
+        grad = torch.empty_like(a)
+        _launch(a.device, _lib.lib().ssg_spsr_map_backward, _ptr(a), _ptr(_f32c(grad_map)), B * C, H, W, _ptr(grad))
+        return grad.to(ctx.in_dtype)
+
+
+def gradient_map(x):
+    """SPSR's gradient map of a (B,C,H,W) batch, any C: Get_gradient(x) and Get_gradient_nopadding(x), which are the same
+    arithmetic.  Differentiable once; fp16 / bf16 inputs are computed in fp32."""
+    return _GradientMapFn.apply(x)
+
+
+class _GradientLossFn(torch.autograd.Function):
+    """scale * sum crit(G(sr) - G(gt)) in one ssg_spsr_loss launch (plus the partials' fold), G(sr) written beside it
+    when asked; backward: ONE ssg_spsr_loss_backward launch for the loss's gradient and the emitted map's together."""
+
+    @staticmethod
+    def forward(ctx, sr, gt, kind, eps, scale, want_map):
+        planes, H, W = _planes("gradient_loss", sr, gt)
+        x, t = _f32c(sr), _f32c(gt)
+        m = torch.empty_like(x) if want_map else None
+        total = _sum_call(x.device, _lib.lib().ssg_spsr_loss, _ptr(x), _ptr(t), planes, H, W, kind, eps, _ptr(m))
+        if ctx.needs_input_grad[0]:
+            ctx.save_for_backward(x, t)
+        ctx.set_materialize_grads(False)
+        ctx.call, ctx.scale, ctx.in_dtype = (planes, H, W, kind, eps), scale, sr.dtype
+        loss = (total[0] * scale).to(torch.float32)
+        return (loss, m.to(sr.dtype)) if want_map else loss
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_loss, g_map=None):
+        x, t = ctx.saved_tensors
+        planes, H, W, kind, eps = ctx.call
+        grad = torch.empty_like(x)
+        gm = None if g_map is None else _f32c(g_map)
+        _launch(x.device, _lib.lib().ssg_spsr_loss_backward, _ptr(x), _ptr(t), _ptr(gm),
+                _ptr(_coef(g_loss, ctx.scale, x.device)), planes, H, W, kind, eps, _ptr(grad))
+        return grad.to(ctx.in_dtype), None, None, None, None, None
+
+
+def _scale(name, reduction, loss_weight, n):
+    return float(loss_weight) / n if _reduction_is_mean(name, reduction) else float(loss_weight)
+
+
+def gradient_loss(sr, gt, kind='mse', eps=1e-12, loss_weight=1.0, reduction='mean', want_map=False):
+    """loss_weight * crit(gradient_map(sr), gradient_map(gt)) without either map in memory (spsrssl_model.py:363):
+    kind 'l1' | 'mse' | 'charbonnier' (with its eps), reduction 'mean' | 'sum'.  want_map=True returns (loss,
+    gradient_map(sr)): both are differentiable with respect to `sr`, through one backward launch."""
+    kind, eps = _pixel_kind(kind, eps)
+    _no_target_grad("gradient_loss", gt)
+    return _GradientLossFn.apply(sr, gt, kind, eps, _scale("gradient_loss", reduction, loss_weight, sr.numel()),
+                                 bool(want_map))
+
+
+class _BranchLossFn(torch.autograd.Function):
+    """scale * sum crit(branch - G(gt)), G(gt) never stored; the gradient goes to `branch`."""
+
+    @staticmethod
+    def forward(ctx, branch, gt, kind, eps, scale):
+        planes, H, W = _planes("gradient_branch_loss", branch, gt)
+        b, t = _f32c(branch), _f32c(gt)
+        total = _sum_call(b.device, _lib.lib().ssg_spsr_branch_loss, _ptr(b), _ptr(t), planes, H, W, kind, eps)
+        if ctx.needs_input_grad[0]:
+            ctx.save_for_backward(b, t)
+        ctx.call, ctx.scale, ctx.in_dtype = (planes, H, W, kind, eps), scale, branch.dtype
+        return (total[0] * scale).to(torch.float32)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        b, t = ctx.saved_tensors
+        grad = torch.empty_like(b)
+        _launch(b.device, _lib.lib().ssg_spsr_branch_grad, _ptr(b), _ptr(t), *ctx.call,
+                _ptr(_coef(g, ctx.scale, b.device)), _ptr(grad))
+        return grad.to(ctx.in_dtype), None, None, None, None
+
+
+def gradient_branch_loss(branch, gt, kind='l1', eps=1e-12, loss_weight=1.0, reduction='mean'):
+    """loss_weight * crit(branch, gradient_map(gt)) (spsrssl_model.py:368), the map formed on the fly; the gradient goes
+    to `branch` only."""
+    kind, eps = _pixel_kind(kind, eps)
+    _no_target_grad("gradient_branch_loss", gt)
+    return _BranchLossFn.apply(branch, gt, kind, eps,
+                               _scale("gradient_branch_loss", reduction, loss_weight, branch.numel()))
+
+
+class _PixelLossFn(torch.autograd.Function):
+    """scale * sum crit(pred - target) of two fp32 tensors of one shape: ssg_pixel_sums, backward ssg_pixel_grad."""
+
+    @staticmethod
+    def forward(ctx, pred, target, kind, eps, scale):
+        a, b = _f32c(pred), _f32c(target)
+        total = _sum_call(a.device, _lib.lib().ssg_pixel_sums, _ptr(a), _ptr(b), a.numel(), kind, eps)
+        if ctx.needs_input_grad[0]:
+            ctx.save_for_backward(a, b)
+        ctx.call, ctx.scale, ctx.in_dtype = (kind, eps), scale, pred.dtype
+        return (total[0] * scale).to(torch.float32)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        a, b = ctx.saved_tensors
+        grad = torch.empty_like(a)
+        _launch(a.device, _lib.lib().ssg_pixel_grad, _ptr(a), _ptr(b), a.numel(), *ctx.call,
+                _ptr(_coef(g, ctx.scale, a.device)), _ptr(grad))
+        return grad.to(ctx.in_dtype), None, None, None, None
+
+
+def pixel_loss(pred, target, kind='mse', eps=1e-12, loss_weight=1.0, reduction='mean'):
+    """loss_weight * crit(pred, target) of two tensors of one shape in one streaming pass each way (MSELoss,
+    CharbonnierLoss); the gradient goes to `pred` only."""
+    kind, eps = _pixel_kind(kind, eps)
+    _need_gpu(pred, target)
+    if pred.shape != target.shape or pred.numel() == 0:
+        raise ValueError(f"ssl_amd: pixel_loss takes two non-empty tensors of one shape, got {tuple(pred.shape)} and "
+                         f"{tuple(target.shape)}")
+    _no_target_grad("pixel_loss", target)
+    return _PixelLossFn.apply(pred, target, kind, eps, _scale("pixel_loss", reduction, loss_weight, pred.numel()))

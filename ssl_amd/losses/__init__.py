@@ -4,3 +4,4 @@ from .lazy import LazySSG, lazy_enabled, set_lazy  # noqa: F401
 from .bebygan import BBL, BackProjectionLoss, BestBuddyLoss, get_flat_mask, imresize  # noqa: F401
 from .ssim import SSIMLoss, create_window, gaussian, ssim  # noqa: F401
 from .gan_loss import GANLoss, MultiScaleGANLoss  # noqa: F401
+from .spsr import CharbonnierLoss, Get_gradient, Get_gradient_nopadding, GradientLoss, MSELoss  # noqa: F401
