@@ -1484,18 +1484,31 @@ size_t ssg_gan_workspace_bytes(void) { return gan_workspace_bytes(); }
 
 int ssg_gan_grid_cap(void) { return gan_grid_cap(); }
 
+// ---- the GAN criteria, SPSR's gradient map and the pixel criteria: every refusal is decided here, before any launch ----
+static bool unaligned(const void *p, size_t a) { return p && (size_t)p % a; }
+
+static int gan_check(const float *x, size_t n, int kind, float sign) {
+  if (!x || n == 0 || kind < SSG_GAN_BCE || kind > SSG_GAN_HINGE || !(sign == 1.f || sign == -1.f)) return SSG_E_BADARG;
+  return unaligned(x, 4) ? SSG_E_ALIGN : 0;   // (the head / float4 split assumes a float's own alignment)
+}
+
 int ssg_gan_sums(const float *x, size_t n, int kind, float sign, float label, const float *shift, void *workspace,
                  double *sums_out, ssg_stream_t stream) {
+  if (const int rc = gan_check(x, n, kind, sign)) return rc;
+  if (!workspace || !sums_out) return SSG_E_BADARG;
+  if (unaligned(workspace, 8) || unaligned(sums_out, 8)) return SSG_E_ALIGN;
   return launch_gan_sums(x, n, kind, sign, label, shift, workspace, sums_out, (hipStream_t)stream);
 }
 
 int ssg_gan_grad(const float *x, size_t n, int kind, float sign, float label, const float *shift, const double *coef,
                  float *grad, ssg_stream_t stream) {
+  if (const int rc = gan_check(x, n, kind, sign)) return rc;
+  if (!coef || !grad) return SSG_E_BADARG;
+  if (unaligned(coef, 8) || unaligned(grad, 4)) return SSG_E_ALIGN;
   return launch_gan_grad(x, n, kind, sign, label, shift, coef, grad, (hipStream_t)stream);
 }
 
-// ---- (R) SPSR's gradient map and the pixel criteria: every refusal is decided here, before any launch ----
-static bool spsr_unaligned(const void *p, size_t a) { return p && (size_t)p % a; }
+// ---- (R) SPSR's gradient map and the pixel criteria ----
 
 static int spsr_check_planes(int planes, int H, int W) {
   if (planes < 1 || H < 1 || W < 1) return SSG_E_BADARG;
@@ -1514,7 +1527,7 @@ int ssg_spsr_grid_cap(void) { return spsr_grid_cap(); }
 int ssg_spsr_map(const float *x, int planes, int H, int W, float *map, ssg_stream_t stream) {
   if (!x || !map) return SSG_E_BADARG;
   if (const int rc = spsr_check_planes(planes, H, W)) return rc;
-  if (spsr_unaligned(x, 4) || spsr_unaligned(map, 4)) return SSG_E_ALIGN;
+  if (unaligned(x, 4) || unaligned(map, 4)) return SSG_E_ALIGN;
   return launch_spsr_map(x, planes, H, W, map, (hipStream_t)stream);
 }
 
@@ -1522,7 +1535,7 @@ int ssg_spsr_map_backward(const float *x, const float *grad_map, int planes, int
                           ssg_stream_t stream) {
   if (!x || !grad_map || !grad_x) return SSG_E_BADARG;
   if (const int rc = spsr_check_planes(planes, H, W)) return rc;
-  if (spsr_unaligned(x, 4) || spsr_unaligned(grad_map, 4) || spsr_unaligned(grad_x, 4)) return SSG_E_ALIGN;
+  if (unaligned(x, 4) || unaligned(grad_map, 4) || unaligned(grad_x, 4)) return SSG_E_ALIGN;
   return launch_spsr_gather(x, nullptr, grad_map, nullptr, planes, H, W, SSG_PIX_L1, 0.f, grad_x, (hipStream_t)stream);
 }
 
@@ -1531,8 +1544,8 @@ int ssg_spsr_loss(const float *x, const float *target, int planes, int H, int W,
   if (!x || !target || !workspace || !sum_out) return SSG_E_BADARG;
   if (const int rc = spsr_check_planes(planes, H, W)) return rc;
   if (const int rc = spsr_check_kind(kind, eps)) return rc;
-  if (spsr_unaligned(x, 4) || spsr_unaligned(target, 4) || spsr_unaligned(map_out, 4) || spsr_unaligned(workspace, 8) ||
-      spsr_unaligned(sum_out, 8))
+  if (unaligned(x, 4) || unaligned(target, 4) || unaligned(map_out, 4) || unaligned(workspace, 8) ||
+      unaligned(sum_out, 8))
     return SSG_E_ALIGN;
   return launch_spsr_loss(x, target, planes, H, W, kind, eps, map_out, workspace, sum_out, (hipStream_t)stream);
 }
@@ -1542,8 +1555,8 @@ int ssg_spsr_loss_backward(const float *x, const float *target, const float *gra
   if (!x || !target || !coef || !grad_x) return SSG_E_BADARG;
   if (const int rc = spsr_check_planes(planes, H, W)) return rc;
   if (const int rc = spsr_check_kind(kind, eps)) return rc;
-  if (spsr_unaligned(x, 4) || spsr_unaligned(target, 4) || spsr_unaligned(grad_map, 4) || spsr_unaligned(grad_x, 4) ||
-      spsr_unaligned(coef, 8))
+  if (unaligned(x, 4) || unaligned(target, 4) || unaligned(grad_map, 4) || unaligned(grad_x, 4) ||
+      unaligned(coef, 8))
     return SSG_E_ALIGN;
   return launch_spsr_gather(x, target, grad_map, coef, planes, H, W, kind, eps, grad_x, (hipStream_t)stream);
 }
@@ -1553,7 +1566,7 @@ int ssg_spsr_branch_loss(const float *branch, const float *gt, int planes, int H
   if (!branch || !gt || !workspace || !sum_out) return SSG_E_BADARG;
   if (const int rc = spsr_check_planes(planes, H, W)) return rc;
   if (const int rc = spsr_check_kind(kind, eps)) return rc;
-  if (spsr_unaligned(branch, 4) || spsr_unaligned(gt, 4) || spsr_unaligned(workspace, 8) || spsr_unaligned(sum_out, 8))
+  if (unaligned(branch, 4) || unaligned(gt, 4) || unaligned(workspace, 8) || unaligned(sum_out, 8))
     return SSG_E_ALIGN;
   return launch_spsr_branch_sums(branch, gt, planes, H, W, kind, eps, workspace, sum_out, (hipStream_t)stream);
 }
@@ -1563,7 +1576,7 @@ int ssg_spsr_branch_grad(const float *branch, const float *gt, int planes, int H
   if (!branch || !gt || !coef || !grad_branch) return SSG_E_BADARG;
   if (const int rc = spsr_check_planes(planes, H, W)) return rc;
   if (const int rc = spsr_check_kind(kind, eps)) return rc;
-  if (spsr_unaligned(branch, 4) || spsr_unaligned(gt, 4) || spsr_unaligned(grad_branch, 4) || spsr_unaligned(coef, 8))
+  if (unaligned(branch, 4) || unaligned(gt, 4) || unaligned(grad_branch, 4) || unaligned(coef, 8))
     return SSG_E_ALIGN;
   return launch_spsr_branch_grad(branch, gt, planes, H, W, kind, eps, coef, grad_branch, (hipStream_t)stream);
 }
@@ -1572,7 +1585,7 @@ int ssg_pixel_sums(const float *pred, const float *target, size_t n, int kind, f
                    double *sum_out, ssg_stream_t stream) {
   if (!pred || !target || !workspace || !sum_out || n < 1) return SSG_E_BADARG;
   if (const int rc = spsr_check_kind(kind, eps)) return rc;
-  if (spsr_unaligned(pred, 4) || spsr_unaligned(target, 4) || spsr_unaligned(workspace, 8) || spsr_unaligned(sum_out, 8))
+  if (unaligned(pred, 4) || unaligned(target, 4) || unaligned(workspace, 8) || unaligned(sum_out, 8))
     return SSG_E_ALIGN;
   return launch_pixel_sums(pred, target, n, kind, eps, workspace, sum_out, (hipStream_t)stream);
 }
@@ -1581,7 +1594,7 @@ int ssg_pixel_grad(const float *pred, const float *target, size_t n, int kind, f
                    float *grad_pred, ssg_stream_t stream) {
   if (!pred || !target || !coef || !grad_pred || n < 1) return SSG_E_BADARG;
   if (const int rc = spsr_check_kind(kind, eps)) return rc;
-  if (spsr_unaligned(pred, 4) || spsr_unaligned(target, 4) || spsr_unaligned(grad_pred, 4) || spsr_unaligned(coef, 8))
+  if (unaligned(pred, 4) || unaligned(target, 4) || unaligned(grad_pred, 4) || unaligned(coef, 8))
     return SSG_E_ALIGN;
   return launch_pixel_grad(pred, target, n, kind, eps, coef, grad_pred, (hipStream_t)stream);
 }

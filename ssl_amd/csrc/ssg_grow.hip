@@ -17,7 +17,7 @@
 // Rows that live in the tile-major region of a k_s = 49 call (negative row scale) are not touched by ssg_grad_rows:
 // ssg_rows_tm (fused step) / ssg_rows_tm_mat (materialising call: it also writes the normalised SSG rows) below walk
 // them with lanes = pixels, and the dense backward forms their G itself.
-#include "ssg_host.hpp"
+#include "ssg_stream.hpp"
 
 namespace ssg {
 
@@ -564,10 +564,11 @@ int launch_rows_tm(const TmRowsParams &p, int ks, int kw, hipStream_t st) {
 // applied to SSG tensors that already exist -- the eager `similarity_map` path and every fallback of the deferred
 // handles).  One streaming pass gives both sums (fp32 inside a lane's ~100 elements, fp64 from there on, fixed order:
 // bit-reproducible); one pass gives d(c1 sum|a-b| + c2 sum kl)/da with the two coefficients read on the device.
+// The element walk is this entry point's own (no head: `vec` is decided by a | b); the workgroup partials and their fold
+// are ssg_stream.hpp's.
 constexpr int CRIT_GRID = 2048;
 
 __global__ __launch_bounds__(256) void criteria_sums_kernel(const float *a, const float *b, size_t n, double *part) {
-  __shared__ double w1[4], w2[4];
   float l1 = 0.f, kl = 0.f;
   const size_t n4 = n / 4, stride = (size_t)gridDim.x * 256;
   const float4 *a4 = (const float4 *)a, *b4 = (const float4 *)b;
@@ -597,43 +598,7 @@ __global__ __launch_bounds__(256) void criteria_sums_kernel(const float *a, cons
   }
   L1 += (double)l1;
   KL += (double)kl;
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    L1 += __shfl_down(L1, o, 64);
-    KL += __shfl_down(KL, o, 64);
-  }
-  if ((threadIdx.x & 63) == 0) {
-    w1[threadIdx.x >> 6] = L1;
-    w2[threadIdx.x >> 6] = KL;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    part[2 * blockIdx.x] = (w1[0] + w1[1]) + (w1[2] + w1[3]);
-    part[2 * blockIdx.x + 1] = (w2[0] + w2[1]) + (w2[2] + w2[3]);
-  }
-}
-
-__global__ __launch_bounds__(256) void criteria_finish_kernel(const double *part, int nparts, float *out) {
-  __shared__ double s1[256], s2[256];
-  double x = 0.0, y = 0.0;
-  for (int i = threadIdx.x; i < nparts; i += 256) {
-    x += part[2 * i];
-    y += part[2 * i + 1];
-  }
-  s1[threadIdx.x] = x;
-  s2[threadIdx.x] = y;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if ((int)threadIdx.x < o) {
-      s1[threadIdx.x] += s1[threadIdx.x + o];
-      s2[threadIdx.x] += s2[threadIdx.x + o];
-    }
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) {
-    out[0] = (float)s1[0];
-    out[1] = (float)s2[0];
-  }
+  stream::workgroup_partials<2>({L1, KL}, part);
 }
 
 __global__ __launch_bounds__(256) void criteria_grad_kernel(const float *a, const float *b, size_t n, const float *coef,
@@ -665,7 +630,9 @@ int launch_criteria_sums(const float *a, const float *b, size_t n, void *scratch
   const size_t want = (n / 4 + 255) / 256;
   const unsigned grid = (unsigned)(want < 1 ? 1 : (want > CRIT_GRID ? CRIT_GRID : want));
   hipLaunchKernelGGL(criteria_sums_kernel, dim3(grid), dim3(256), 0, st, a, b, n, (double *)scratch);
-  hipLaunchKernelGGL(criteria_finish_kernel, dim3(1), dim3(256), 0, st, (const double *)scratch, (int)grid, sums_out);
+  // (always folded, a single workgroup's pair included: the partials are fp64 in the scratch, the result is fp32)
+  hipLaunchKernelGGL((stream::fold_kernel<2, float>), dim3(1), dim3(256), 0, st, (const double *)scratch, (int)grid,
+                     sums_out);
   return (int)hipGetLastError();
 }
 

@@ -976,27 +976,27 @@ def gradient_loss(sr, gt, kind='mse', eps=1e-12, loss_weight=1.0, reduction='mea
                                  bool(want_map))
 
 
-class _BranchLossFn(torch.autograd.Function):
-    """scale * sum crit(branch - G(gt)), G(gt) never stored; the gradient goes to `branch`."""
+class _StreamLossFn(torch.autograd.Function):
+    """scale * sum crit(first, second) in one streaming pass each way, the gradient going to `first` alone: the branch
+    loss and the pixel criteria.  `sums(a, b)` makes the family's sums call on the fp32 tensors and returns the fp64
+    (1,) sum; `grad(a, b, coef, out)` makes its gradient call (the pattern of _FusedLossFn)."""
 
     @staticmethod
-    def forward(ctx, branch, gt, kind, eps, scale):
-        planes, H, W = _planes("gradient_branch_loss", branch, gt)
-        b, t = _f32c(branch), _f32c(gt)
-        total = _sum_call(b.device, _lib.lib().ssg_spsr_branch_loss, _ptr(b), _ptr(t), planes, H, W, kind, eps)
+    def forward(ctx, first, second, scale, sums, grad):
+        a, b = _f32c(first), _f32c(second)
+        total = sums(a, b)
         if ctx.needs_input_grad[0]:
-            ctx.save_for_backward(b, t)
-        ctx.call, ctx.scale, ctx.in_dtype = (planes, H, W, kind, eps), scale, branch.dtype
+            ctx.save_for_backward(a, b)
+        ctx.grad_call, ctx.scale, ctx.in_dtype = grad, scale, first.dtype
         return (total[0] * scale).to(torch.float32)
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, g):
-        b, t = ctx.saved_tensors
-        grad = torch.empty_like(b)
-        _launch(b.device, _lib.lib().ssg_spsr_branch_grad, _ptr(b), _ptr(t), *ctx.call,
-                _ptr(_coef(g, ctx.scale, b.device)), _ptr(grad))
-        return grad.to(ctx.in_dtype), None, None, None, None
+        a, b = ctx.saved_tensors
+        out = torch.empty_like(a)
+        ctx.grad_call(a, b, _ptr(_coef(g, ctx.scale, a.device)), _ptr(out))
+        return out.to(ctx.in_dtype), None, None, None, None
 
 
 def gradient_branch_loss(branch, gt, kind='l1', eps=1e-12, loss_weight=1.0, reduction='mean'):
@@ -1004,30 +1004,12 @@ def gradient_branch_loss(branch, gt, kind='l1', eps=1e-12, loss_weight=1.0, redu
     to `branch` only."""
     kind, eps = _pixel_kind(kind, eps)
     _no_target_grad("gradient_branch_loss", gt)
-    return _BranchLossFn.apply(branch, gt, kind, eps,
-                               _scale("gradient_branch_loss", reduction, loss_weight, branch.numel()))
-
-
-class _PixelLossFn(torch.autograd.Function):
-    """scale * sum crit(pred - target) of two fp32 tensors of one shape: ssg_pixel_sums, backward ssg_pixel_grad."""
-
-    @staticmethod
-    def forward(ctx, pred, target, kind, eps, scale):
-        a, b = _f32c(pred), _f32c(target)
-        total = _sum_call(a.device, _lib.lib().ssg_pixel_sums, _ptr(a), _ptr(b), a.numel(), kind, eps)
-        if ctx.needs_input_grad[0]:
-            ctx.save_for_backward(a, b)
-        ctx.call, ctx.scale, ctx.in_dtype = (kind, eps), scale, pred.dtype
-        return (total[0] * scale).to(torch.float32)
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, g):
-        a, b = ctx.saved_tensors
-        grad = torch.empty_like(a)
-        _launch(a.device, _lib.lib().ssg_pixel_grad, _ptr(a), _ptr(b), a.numel(), *ctx.call,
-                _ptr(_coef(g, ctx.scale, a.device)), _ptr(grad))
-        return grad.to(ctx.in_dtype), None, None, None, None
+    call = _planes("gradient_branch_loss", branch, gt) + (kind, eps)
+    L = _lib.lib()
+    return _StreamLossFn.apply(
+        branch, gt, _scale("gradient_branch_loss", reduction, loss_weight, branch.numel()),
+        lambda b, t: _sum_call(b.device, L.ssg_spsr_branch_loss, _ptr(b), _ptr(t), *call),
+        lambda b, t, coef, out: _launch(b.device, L.ssg_spsr_branch_grad, _ptr(b), _ptr(t), *call, coef, out))
 
 
 def pixel_loss(pred, target, kind='mse', eps=1e-12, loss_weight=1.0, reduction='mean'):
@@ -1039,4 +1021,8 @@ def pixel_loss(pred, target, kind='mse', eps=1e-12, loss_weight=1.0, reduction='
         raise ValueError(f"ssl_amd: pixel_loss takes two non-empty tensors of one shape, got {tuple(pred.shape)} and "
                          f"{tuple(target.shape)}")
     _no_target_grad("pixel_loss", target)
-    return _PixelLossFn.apply(pred, target, kind, eps, _scale("pixel_loss", reduction, loss_weight, pred.numel()))
+    L = _lib.lib()
+    return _StreamLossFn.apply(
+        pred, target, _scale("pixel_loss", reduction, loss_weight, pred.numel()),
+        lambda a, b: _sum_call(a.device, L.ssg_pixel_sums, _ptr(a), _ptr(b), a.numel(), kind, eps),
+        lambda a, b, coef, out: _launch(a.device, L.ssg_pixel_grad, _ptr(a), _ptr(b), a.numel(), kind, eps, coef, out))

@@ -25,6 +25,10 @@ SHAPES = {"1x1x1x1": (1, 1, 1, 1), "1x1x1x7": (1, 1, 1, 7), "1x1x7x1": (1, 1, 7,
           "2x3x9x11": (2, 3, 9, 11), "1x3x5x64": (1, 3, 5, 64), "1x3x5x65": (1, 3, 5, 65), "view": (2, 3, 9, 12),
           "mixed": (2, 3, 9, 12), "strided": (2, 3, 9, 11), "folded": (2, 3, 20, 23)}
 CONTENTS = ("uniform", "flat", "step", "checker", "same")
+# the layouts that start k floats into a buffer; HEADS_SHAPE's 11 elements at k = 1, 2, 3 leave a head of 3, 2, 1, two
+# groups of four and a tail of 0, 1, 2
+OFFSET_VIEWS = {"view": 1, "view2": 2, "view3": 3}
+HEADS_SHAPE = (1, 1, 1, 11)
 
 
 def content(name, shape, seed=0):
@@ -49,11 +53,12 @@ def content(name, shape, seed=0):
 
 def place(t, how, dev):
     """The CPU tensor t on the device as the case `how` wants it laid out."""
-    if how == "view":                   # one float behind a 16-byte boundary: a scalar head of three elements
+    if how in OFFSET_VIEWS:             # k floats behind a 16-byte boundary: a scalar head of 4 - k elements
+        k = OFFSET_VIEWS[how]
         buf = torch.zeros(t.numel() + 5, dtype=torch.float32, device=dev)
-        v = buf[1:1 + t.numel()].view(t.shape)
+        v = buf[k:k + t.numel()].view(t.shape)
         v.copy_(t)
-        assert v.data_ptr() % 16 == 4 and v.is_contiguous()
+        assert v.data_ptr() % 16 == 4 * k and v.is_contiguous()
         return v
     if how == "strided":                # every second column of a buffer twice as wide
         buf = torch.zeros(t.shape[:-1] + (2 * t.shape[-1],), dtype=torch.float32, device=dev)

@@ -373,6 +373,17 @@ def test_criteria_trip_sizes_cross_the_grid_caps():
     assert CRITERIA_FLUSH_N // 4 == 33 * grid * 256 and 128 * grid * 256 < CRITERIA_FLUSH_N - 1 < 256 * grid * 256
 
 
+def test_streaming_criteria_sizes_and_grid_caps():
+    """The workspaces and grid caps of the kernels built on ssg_stream.hpp (host arithmetic only): two fp64 per workgroup
+    of the GAN sums, one of SPSR's and the pixel criteria's, at most 1,024 workgroups each; two fp64 for each of the old
+    criteria's 2,048.  Callers size their buffers by these and the GPU tests compute their trip shapes from the caps."""
+    from ssl_amd import _lib
+    L = _lib.lib()
+    assert L.ssg_gan_workspace_bytes() == 16384 and L.ssg_gan_grid_cap() == 1024
+    assert L.ssg_spsr_workspace_bytes() == 8192 and L.ssg_spsr_grid_cap() == 1024
+    assert L.ssg_criteria_scratch_bytes() == 32768
+
+
 def test_workspace_layout_of_the_fused_call():
     """ssg_loss_workspace_layout (host arithmetic only): the pieces lie in order inside ssg_loss_workspace_bytes(), the
     row-major scratch rows of the fused step behind them, and -- k_s = 49 only -- two tile-major regions of capacity / 128

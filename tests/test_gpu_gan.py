@@ -34,13 +34,15 @@ def _crit(gan_type, labels=(1.0, 0.0), weight=C.WEIGHT, multi=False):
 
 
 def _to_device(x, dev, offset):
-    """x on the device as a leaf; offset: as a view that starts one float into its buffer (not 16-byte aligned)."""
+    """x on the device as a leaf; offset: as a view that starts that many floats (True: one) into its buffer (not 16-byte
+    aligned)."""
     if not offset:
         return x.to(dev)
-    buf = torch.empty(x.numel() + 1, dtype=x.dtype, device=dev)
-    v = buf[1:].view(x.shape)
+    k = int(offset)
+    buf = torch.empty(x.numel() + k, dtype=x.dtype, device=dev)
+    v = buf[k:].view(x.shape)
     v.copy_(x)
-    assert v.data_ptr() % 16 == 4 and v.is_contiguous()
+    assert v.data_ptr() % 16 == 4 * k and v.is_contiguous()
     return v
 
 
@@ -282,6 +284,43 @@ def test_offset_gradient_takes_the_wide_stores_to_the_same_bits(dev):
         d = R.delta(x, 0.375)
         want = 0.25 * R.dell(d, kind, -1.0, R.fl32(0.9)) - 0.125
         _within(outs[0], want, R.grad_bound(d, (kind, -1.0, R.fl32(0.9)), 0.25) + R.U * want.abs(), f"C ABI kind {kind}")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("offset", (0, 1, 2, 3))
+def test_heads_and_tails_of_one_two_and_three(dev, offset):
+    """Eleven elements 0, 1, 2 and 3 floats behind a 16-byte boundary: a scalar head of 0, 3, 2 and 1, two float4, a tail
+    of 3, 0, 1 and 2.  The sums and the gradient through the module (its gradient buffer is aligned), then the gradient
+    through the C ABI into a buffer with the input's own alignment (16-byte stores) and into one a float further (stored
+    one by one): the same bits."""
+    from ssl_amd import _lib
+    L = _lib.lib()
+    x = C.content("special", (11,))
+    d = R.delta(x)
+    for config in C.CONFIGS:
+        gan_type, labels, real, disc, upstream = config
+        w = 1.0 if disc else C.WEIGHT
+        sp = R.spec(gan_type, real, disc, *labels)
+        want_l, want_g = R.plain(x, sp, w, upstream)
+        loss, grad, node = _plain(dev, x, config, offset=offset)
+        assert "PlainCriterion" in node
+        what = f"offset {offset} {gan_type} labels={labels} real={real} disc={disc}"
+        _within(loss, want_l, R.loss_bound(d, sp, w), what + " loss")
+        _within(grad, want_g, R.grad_bound(d, sp, upstream * w / d.numel()), what + " grad")
+    a = _to_device(x, dev, offset)
+    coef = torch.tensor([0.25, -0.125], dtype=torch.float64, device=dev)
+    stream = torch.cuda.current_stream().cuda_stream
+    for kind in range(5):
+        outs = []
+        for off in (offset, (offset + 1) % 4):
+            buf = torch.zeros(11 + 8, dtype=torch.float32, device=dev)
+            g = buf[off:off + 11]
+            _lib.check(L.ssg_gan_grad(a.data_ptr(), 11, kind, 1.0, 0.9, None, coef.data_ptr(), g.data_ptr(), stream))
+            assert not bool(buf[:off].any()) and not bool(buf[off + 11:].any())      # nothing outside the 11
+            outs.append(g.clone())
+        assert torch.equal(_bits(outs[0]), _bits(outs[1]))
+        want = 0.25 * R.dell(d, kind, 1.0, R.fl32(0.9)) - 0.125
+        _within(outs[0], want, R.grad_bound(d, (kind, 1.0, R.fl32(0.9)), 0.25) + R.U * want.abs(), f"C ABI kind {kind}")
 
 
 @pytest.mark.gpu

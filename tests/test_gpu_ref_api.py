@@ -468,7 +468,7 @@ def _criteria_against_fp64(dev, n, views, reductions, seed):
 
 
 def test_criterion_kernels_past_one_grid_trip(dev):
-    """criteria_sums_kernel's second trip on both paths with criteria_finish_kernel folding all 2,048 slots, and
+    """criteria_sums_kernel's second trip on both paths with fold_kernel<2, float> folding all 2,048 slots, and
     criteria_grad_kernel's second trip on its aligned path (the unaligned one is past its grid at either size)."""
     _criteria_against_fp64(dev, CRITERIA_SUMS_TRIP_N, ((0, CRITERIA_SUMS_TRIP_N), (1, CRITERIA_SUMS_TRIP_N)),
                            ("mean", "sum"), 21)

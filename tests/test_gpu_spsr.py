@@ -185,6 +185,55 @@ def test_a_second_grid_trip(dev):
     run_case(xc, tc, "view", dev, kinds=("l1",), check=False)     # (its own asserts: loss and map bits of both forms)
 
 
+@pytest.mark.parametrize("how", list(C.OFFSET_VIEWS))
+def test_heads_and_tails_of_one_two_and_three(dev, how):
+    """Eleven elements 1, 2 and 3 floats behind a 16-byte boundary: a scalar head of 3, 2 and 1, two groups of four, a
+    tail of 0, 1 and 2, in every kernel built on the shared walk (the outputs are aligned: stored one by one)."""
+    xc, tc = C.content("uniform", C.HEADS_SHAPE, 13)
+    run_case(xc, tc, how, dev)
+
+
+@pytest.mark.parametrize("how", list(C.OFFSET_VIEWS))
+def test_offset_outputs_take_the_wide_stores_to_the_same_bits(dev, how):
+    """Through the C ABI an output with the input's own misalignment is stored 16 bytes wide behind the scalar head, one
+    a float further element by element: the same bits, nothing outside the eleven elements, and within the bound."""
+    from ssl_amd import _lib
+    L = _lib.lib()
+    k, n = C.OFFSET_VIEWS[how], int(np.prod(C.HEADS_SHAPE))
+    xc, tc = C.content("uniform", C.HEADS_SHAPE, 13)
+    brc = C.branch_for(tc)
+    x, t, br = (C.place(v, how, dev) for v in (xc, tc, brc))
+    coef = torch.tensor([0.25], dtype=torch.float64, device=dev)
+    work = torch.empty(L.ssg_spsr_workspace_bytes(), dtype=torch.uint8, device=dev)
+    total = torch.empty(1, dtype=torch.float64, device=dev)
+    stream = torch.cuda.current_stream().cuda_stream
+    H, W = C.HEADS_SHAPE[2:]
+    calls = {
+        "map": lambda o: L.ssg_spsr_map(x.data_ptr(), 1, H, W, o, stream),
+        "loss map": lambda o: L.ssg_spsr_loss(x.data_ptr(), t.data_ptr(), 1, H, W, 1, 0.0, o, work.data_ptr(),
+                                              total.data_ptr(), stream),
+        "branch grad": lambda o: L.ssg_spsr_branch_grad(br.data_ptr(), t.data_ptr(), 1, H, W, 0, 0.0, coef.data_ptr(), o,
+                                                        stream),
+        "pixel grad": lambda o: L.ssg_pixel_grad(x.data_ptr(), t.data_ptr(), n, 2, 1e-12, coef.data_ptr(), o, stream),
+    }
+    outs = {}
+    for name, call in calls.items():
+        got = []
+        for off in (k, (k + 1) % 4):           # the input's own offset: wide; a float further: one by one
+            buf = torch.zeros(n + 8, dtype=torch.float32, device=dev)
+            _lib.check(call(buf[off:].data_ptr()))
+            assert not bool(buf[:off].any()) and not bool(buf[off + n:].any()), (name, off)
+            got.append(buf[off:off + n].clone())
+        assert torch.equal(_bits(got[0]), _bits(got[1])), name
+        outs[name] = got[0].view(C.HEADS_SHAPE)
+    hold("map", outs["map"], R.gmap(xc), R.map_bound(xc))
+    hold("map", outs["loss map"], R.gmap(xc), R.map_bound(xc))
+    want = R.branch_loss(brc, tc, "l1", 0.0, 0.25)
+    hold("branch loss l1 gradient", outs["branch grad"], want.grad, want.grad_bound)
+    want = R.pixel(xc, tc, "charbonnier", 1e-12, 0.25)
+    hold("pixel loss charbonnier gradient", outs["pixel grad"], want.grad, want.grad_bound)
+
+
 def test_one_nan_pixel_reaches_its_four_neighbours_and_the_loss(dev):
     from ssl_amd import engine
     xc, tc = C.content("uniform", C.SHAPES["2x3x9x11"], 5)
