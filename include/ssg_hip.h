@@ -74,6 +74,8 @@ typedef void *ssg_stream_t; /* hipStream_t */
 /* 6, additive: + ssg_spsr_map, ssg_spsr_map_backward, ssg_spsr_loss, ssg_spsr_loss_backward, ssg_spsr_branch_loss,
  * ssg_spsr_branch_grad, ssg_pixel_sums, ssg_pixel_grad, ssg_spsr_workspace_bytes, ssg_spsr_grid_cap (SPSR's gradient map
  * and the pixel criteria, section (R)). */
+/* 6, additive: + ssg_multi_apply, ssg_multi_table_fill, ssg_multi_table_bytes, ssg_multi_chunks, ssg_multi_chunk,
+ * ssg_multi_grid_cap (the EMA and copy updates of a parameter set in one launch, section (S)). */
 int ssg_abi_version(void);
 const char *ssg_status_string(int status);
 /* Device-side refusals that no return value can carry (everything is asynchronous): waits for `stream`, then returns
@@ -985,6 +987,56 @@ int ssg_pixel_sums(const float *pred, const float *target, size_t n, int kind, f
                    double *sum_out, ssg_stream_t stream);
 int ssg_pixel_grad(const float *pred, const float *target, size_t n, int kind, float eps, const double *coef,
                    float *grad_pred, ssg_stream_t stream);
+
+/* ---------------------------------------------------------------- (S) ----
+ * The EMA and copy updates of a whole parameter set as ONE launch, whatever the number of tensors
+ * (basicsr/models/base_model.py:75-82 model_ema and train_BSGRAN/models/model_base.py:192-197 update_E,
+ * `ema[k].data.mul_(decay).add_(net[k].data, alpha=1 - decay)` per parameter name; Diffusion-Based-SR's
+ * ldm/modules/ema.py LitEma, `shadow.sub_(one_minus_decay * (shadow - param))` per parameter, and its copy_to / store /
+ * restore), ssl_amd/csrc/ssg_multi.hip.  Tensors are fp32, walked flat over n elements each; a pair (dst, src) updates
+ * dst from src.  Per element, every operation fp32:
+ *   SSG_MT_EMA   e <- fmaf(a, p, fl(e d))        d = (float)decay, a = (float)(1 - decay), the subtraction in double:
+ *                                                torch's e.mul_(decay).add_(p, alpha=1 - decay), bit for bit
+ *   SSG_MT_LIT   e <- e - fl(w fl(e - p))        three roundings, no fma; w = w_dev[0], ONE FLOAT READ ON THE DEVICE
+ *                                                (d and a are checked and not used)
+ *   SSG_MT_COPY  e <- p                          a move of 32-bit words (d, a and w_dev are checked and not used)
+ * Nothing is special-cased: d = 0 with an infinite e gives NaN, as the reference's product does.
+ * The table describes the set and lives ON THE DEVICE; the host builds its image once per parameter set and the image
+ * is reused from call to call.  8-byte words: {n_tensors, n_chunks, chunk, 0}, then (dst address, src address, n) per
+ * tensor, then one word per chunk, tensor index << 32 | index of the chunk inside its tensor, in tensor order and
+ * chunk order.  A chunk is ssg_multi_chunk() elements of one tensor (the last chunk of a tensor what is left); an empty
+ * tensor has a record and no chunk.
+ * ssg_multi_chunks: the set's chunk count, INT_MAX + 1 where it does not fit an int.
+ * ssg_multi_table_bytes: the image's size, 32 + 24 n_tensors + 8 chunks; 0 where ssg_multi_table_fill would refuse the
+ *   counts.
+ * ssg_multi_table_fill: writes the image into `table` (HOST memory, 8-byte aligned) from host arrays of n_tensors dst
+ *   addresses, src addresses and element counts.  Touches no device: the addresses are never dereferenced.
+ * ssg_multi_apply: ONE launch on `stream` for `table` (the image, on the device) and its n_chunks: a workgroup of 256
+ *   threads takes a chunk, and beyond ssg_multi_grid_cap() workgroups takes further chunks grid-stride.  Inside a
+ *   chunk accesses are 16 bytes wide behind a scalar head and in front of a scalar tail wherever dst and src share
+ *   their alignment mod 16, element by element where they do not: a tensor needs only a float's own alignment.
+ *   Stores stay inside [dst, dst + n) of every tensor.  No LDS, no atomics; no allocation, copy, synchronisation or
+ *   host read: the call can be captured into a HIP graph.  n_chunks = 0 launches nothing.  The kernel takes the chunk
+ *   count from the table: n_chunks only sizes the grid.
+ * The caller owns what the table points to: every tensor must be alive and unmoved at each apply, dst ranges must not
+ * overlap each other or a src range other than at the same address.
+ * Status, decided before the launch with every tensor and the table untouched: SSG_E_BADARG for a null table (or null
+ * arrays with n_tensors > 0, or a null address of a non-empty tensor), an unknown kind, a NaN d or a, SSG_MT_LIT without
+ * w_dev; SSG_E_ALIGN for a dst or src address of a non-empty tensor that is not 4-byte aligned (detected by the fill), a
+ * table that is not 8-byte aligned or a w_dev that is not 4-byte aligned; SSG_E_TOOLARGE for a chunk count (of one
+ * tensor or of the set) or a tensor count that does not fit an int; SSG_E_WORKSPACE for a table_bytes below
+ * ssg_multi_table_bytes(). */
+#define SSG_MT_EMA 0
+#define SSG_MT_LIT 1
+#define SSG_MT_COPY 2
+int ssg_multi_chunk(void);
+int ssg_multi_grid_cap(void);
+size_t ssg_multi_chunks(size_t n_tensors, const size_t *counts);
+size_t ssg_multi_table_bytes(size_t n_tensors, const size_t *counts);
+int ssg_multi_table_fill(size_t n_tensors, const size_t *dst, const size_t *src, const size_t *counts,
+                         void *table /* host */, size_t table_bytes);
+int ssg_multi_apply(const void *table /* device */, size_t n_chunks, int kind, float d, float a,
+                    const float *w_dev /* nullable */, ssg_stream_t stream);
 
 #ifdef SSG_PROFILE
 /* PROFILING BUILD ONLY (libssg_hip_prof.so, compiled with -DSSG_PROFILE; the product library libssg_hip.so does not

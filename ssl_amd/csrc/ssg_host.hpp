@@ -146,6 +146,11 @@ int launch_pixel_sums(const float *a, const float *b, size_t n, int kind, float 
 int launch_pixel_grad(const float *a, const float *b, size_t n, int kind, float eps, const double *coef, float *grad,
                       hipStream_t st);
 
+// ---- ssg_multi.hip: the EMA / copy update of a whole parameter set in one launch (entry points beside its kernel) ----
+int multi_chunk();
+int multi_grid_cap();
+int launch_multi_apply(const void *table, size_t n_chunks, int kind, float d, float a, const float *w, hipStream_t st);
+
 // ---- ssg_resample.hip: Pillow's 8-bit convolution resize (entry points beside its kernel) ----
 int resample_ksize(int in, int out, int filter);                                   // host only
 int resample_table(int in, int out, int filter, int *bounds, int *coef);           // host only: fp64, libm's sin / cos
