@@ -1038,6 +1038,101 @@ int ssg_multi_table_fill(size_t n_tensors, const size_t *dst, const size_t *src,
 int ssg_multi_apply(const void *table /* device */, size_t n_chunks, int kind, float d, float a,
                     const float *w_dev /* nullable */, ssg_stream_t stream);
 
+/* ---------------------------------------------------------------- (T) ----
+ * BSRGAN's degradation chain on a RAGGED batch (GAN-Based-SR/train_BSGRAN/utils/utils_blindsr.py: degradation_bsrgan
+ * :443-530, _nocrop :532-616, _ours_p :618-706, _plus :708-792, called once per sample by data/dataset_blindsr.py,
+ * dataset_blindsrmask.py and dataset_blindsroursp.py), ssl_amd/csrc/ssg_blindsr.hip.  Every image has its own stage
+ * order and its own intermediate sizes, so a launch is driven by one record per image, and there is one launch per
+ * operation family and stage slot, whatever the batch.  Images are fp32 planar (C, h, w), C 1 or 3, at ELEMENT offsets
+ * of the launch's `in` and `out` buffers (the two ping-pong arenas; both may be one allocation).
+ *   SSG_BSR_CONV    add_blur :335-346 and downsample2's shifted kernel :497-501:
+ *                   scipy.ndimage.convolve(img, k[:, :, None], mode='mirror')[0::stride, 0::stride], a true convolution
+ *                   (the kernel is flipped), out[y, x] = sum_ij k[i, j] in[fold(y stride + r - i), fold(x stride + r - j)],
+ *                   r = k / 2, fold the reflection of period 2 (n - 1) that does not repeat the edge sample (n = 1: 0).
+ *                   op = k, odd 3 .. 9, its k k fp32 taps row-major at pool_off; stride 1 .. 4; oh = ceil(h / stride).
+ *                   One fmaf per tap, row by row of the window: within (k k + 2) 2^-24 sum |k_ij| |x_ij| of fp64.
+ *   SSG_BSR_RESIZE  cv2.resize(img, (ow, oh), interpolation=op) of a float32 image, :357, :471, :495, :506, :784.
+ *                   Source coordinate (d + 0.5) (n_src / n_dst) - 0.5 in fp64, cast to float, split into floor and
+ *                   fraction; fp32 weights; the horizontal taps of a source row are summed first, then the rows.
+ *                   SSG_BSR_LINEAR two taps, fraction 0 and index clamped at either end; SSG_BSR_CUBIC four taps, A =
+ *                   -0.75, indices clamped; SSG_BSR_AREA: both ratios >= 1 and both integer, the box sum times
+ *                   1 / area; both >= 1 otherwise, OpenCV's area table (cell [d s, d s + s), width min(s, n - d s), end
+ *                   weights kept above 1e-3, not renormalised); otherwise its area-mode linear rule, sx = floor(d s),
+ *                   f = (d + 1) - (sx + 1) / s, 0 where <= 0 and its fractional part otherwise.  Equality with cv2.resize
+ *                   itself is SUPPOSED (OpenCV is not available to the tests); the tests hold the kernel to an fp64
+ *                   restatement of these rules within a bound that counts every rounding.
+ *   SSG_BSR_NOISE   the arithmetic of add_Gaussian_noise :363-377, add_speckle_noise :380-395 and add_Poisson_noise
+ *                   :398-409 around their draws, which are passed in as `field` (C planes at field_off; one plane for
+ *                   the gray forms), p0 a scale (1 for a field that is already the noise) or Poisson's `vals`:
+ *                     GAUSS_COLOR | _GRAY | _CORR      y = x + fl(n p0), n = f_c | f_0 | sum_j M[c][j] f_j, M the 3 x 3 fp32
+ *                                                      matrix at pool_off (numpy's multivariate_normal factor,
+ *                                                      transposed) applied to a standard-normal colour field
+ *                     SPECKLE_COLOR | _GRAY | _CORR    y = x + fl(x fl(n p0)), x clipped first under SSG_BSR_LEAD_CLIP
+ *                     POISSON_RATES                    out_c = fl(q_c p0), q = clip(rint(fl(x 255)), 0, 255) / 255 (float32,
+ *                                                      half to even: numpy's bits)
+ *                     POISSON_COLOR                    y_c = fl(f_c / p0), f the draw
+ *                     POISSON_RATES_GRAY               out_0 = (float)(g p0), g the same quantisation in fp64 of
+ *                                                      fma(q_2, 0.114, fma(q_1, 0.587, 0.299 q_0)), the fused chain of
+ *                                                      numpy's dot: ONE plane is written
+ *                     POISSON_GRAY                     y_c = (float)(q_c + (fl(f_0 / p0) - g)), fp64 as numpy promotes it
+ *                   oh = h, ow = w; the _CORR and gray Poisson forms need C = 3.  Bit-equal to numpy on the same fields.
+ * SSG_BSR_CLIP in flags: np.clip(y, 0, 1) closes the operation (a NaN passes through, as in numpy).
+ * The table lives ON THE DEVICE; ssg_blindsr_table_fill writes its image into HOST memory (4-byte aligned,
+ * ssg_blindsr_table_bytes(n_images) = 16 + 4 roundup4(n_images + 1) + 64 n_images) from n_images records, and CHECKS them:
+ * every range inside in_elems / out_elems / field_elems / pool_elems (the buffers' sizes in elements), no two outputs
+ * overlapping, and with same_buffer != 0 no output overlapping any input.  It computes tile0 and tiles_x and returns the
+ * launch's tile count.  Words: {n_images, n_tiles, family, 0}, the first tile of every image (n_images + 1 words, padded
+ * to four), the records.  A workgroup of 256 threads takes a tile (8 x 32 output pixels of every channel; for noise
+ * 1,024 pixels), the image by binary search in the prefix, and beyond ssg_blindsr_grid_cap() workgroups further tiles
+ * grid-stride.  Every output element has exactly one writer and there are no atomics: the bits of image b do not depend
+ * on the rest of the batch.  The launches allocate, copy and synchronise nothing.
+ * ssg_blindsr_tile: the tile of a family, (8, 32) output pixels for conv and resize, (1, 1024) pixels for noise.
+ * Status: SSG_E_BADARG for a null pointer, an unknown family / op / flag, C not 1 or 3, an empty image, a kernel size or
+ * stride outside the range, sizes that contradict the operation, a NaN p0, overlapping ranges; SSG_E_WORKSPACE for a
+ * range that leaves its buffer or a table_bytes below ssg_blindsr_table_bytes(); SSG_E_TOOLARGE for an image or a tile
+ * count beyond INT_MAX or a buffer beyond 2^32 - 1 elements; SSG_E_ALIGN for a misaligned pointer. */
+#define SSG_BSR_CONV 0
+#define SSG_BSR_RESIZE 1
+#define SSG_BSR_NOISE 2
+#define SSG_BSR_LINEAR 1          /* cv2's interpolation numbers */
+#define SSG_BSR_CUBIC 2
+#define SSG_BSR_AREA 3
+#define SSG_BSR_CLIP 1
+#define SSG_BSR_LEAD_CLIP 2
+#define SSG_BSR_GAUSS_COLOR 0
+#define SSG_BSR_GAUSS_GRAY 1
+#define SSG_BSR_GAUSS_CORR 2
+#define SSG_BSR_SPECKLE_COLOR 3
+#define SSG_BSR_SPECKLE_GRAY 4
+#define SSG_BSR_SPECKLE_CORR 5
+#define SSG_BSR_POISSON_RATES 6
+#define SSG_BSR_POISSON_COLOR 7
+#define SSG_BSR_POISSON_RATES_GRAY 8
+#define SSG_BSR_POISSON_GRAY 9
+typedef struct ssg_blindsr_record {
+  unsigned in_off, out_off;   /* elements into `in` / `out` */
+  int C, h, w, oh, ow;
+  int op;                     /* conv: k; resize: SSG_BSR_LINEAR | CUBIC | AREA; noise: SSG_BSR_GAUSS_COLOR ... */
+  int stride;                 /* conv only */
+  int flags;                  /* SSG_BSR_CLIP | SSG_BSR_LEAD_CLIP */
+  unsigned pool_off;          /* floats into `pool`: the taps or the 3 x 3 matrix */
+  unsigned field_off;         /* elements into `field` (noise) */
+  float p0;                   /* noise: scale or vals */
+  int tile0, tiles_x;         /* written by ssg_blindsr_table_fill */
+  int reserved;
+} ssg_blindsr_record;
+int ssg_blindsr_grid_cap(void);
+int ssg_blindsr_tile(int family, int *tile_rows, int *tile_cols);
+size_t ssg_blindsr_table_bytes(int n_images);
+int ssg_blindsr_table_fill(int family, const ssg_blindsr_record *records, int n_images, size_t in_elems,
+                           size_t out_elems, size_t field_elems, size_t pool_elems, int same_buffer,
+                           void *table /* host */, size_t table_bytes, int *n_tiles_out);
+int ssg_blindsr_conv(const void *table /* device */, int n_tiles, const float *in, float *out, const float *pool,
+                     ssg_stream_t stream);
+int ssg_blindsr_resize(const void *table /* device */, int n_tiles, const float *in, float *out, ssg_stream_t stream);
+int ssg_blindsr_noise(const void *table /* device */, int n_tiles, const float *in, float *out,
+                      const float *field /* nullable */, const float *pool /* nullable */, ssg_stream_t stream);
+
 #ifdef SSG_PROFILE
 /* PROFILING BUILD ONLY (libssg_hip_prof.so, compiled with -DSSG_PROFILE; the product library libssg_hip.so does not
  * export this symbol and has no code path that skips work).  Results are WRONG while a mask is set: skip kernel

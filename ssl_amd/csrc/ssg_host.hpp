@@ -151,6 +151,12 @@ int multi_chunk();
 int multi_grid_cap();
 int launch_multi_apply(const void *table, size_t n_chunks, int kind, float d, float a, const float *w, hipStream_t st);
 
+// ---- ssg_blindsr.hip: BSRGAN's degradation chain on a ragged batch, one launch per operation family (entry points
+// beside its kernels) ----
+int blindsr_grid_cap();
+int launch_blindsr(int family, const void *table, int n_tiles, const float *in, float *out, const float *field,
+                   const float *pool, hipStream_t st);
+
 // ---- ssg_resample.hip: Pillow's 8-bit convolution resize (entry points beside its kernel) ----
 int resample_ksize(int in, int out, int filter);                                   // host only
 int resample_table(int in, int out, int filter, int *bounds, int *coef);           // host only: fp64, libm's sin / cos
