@@ -76,6 +76,8 @@ typedef void *ssg_stream_t; /* hipStream_t */
  * and the pixel criteria, section (R)). */
 /* 6, additive: + ssg_multi_apply, ssg_multi_table_fill, ssg_multi_table_bytes, ssg_multi_chunks, ssg_multi_chunk,
  * ssg_multi_grid_cap (the EMA and copy updates of a parameter set in one launch, section (S)). */
+/* 6, additive: + ssg_mcrit_sums, ssg_mcrit_grad, ssg_mcrit_workspace_bytes, ssg_mcrit_chunk, ssg_mcrit_grid_cap and
+ * SSG_PIX_FRO (a pixel criterion over a ragged set of tensor pairs: the perceptual loss, section (U)). */
 int ssg_abi_version(void);
 const char *ssg_status_string(int status);
 /* Device-side refusals that no return value can carry (everything is asynchronous): waits for `stream`, then returns
@@ -1132,6 +1134,47 @@ int ssg_blindsr_conv(const void *table /* device */, int n_tiles, const float *i
 int ssg_blindsr_resize(const void *table /* device */, int n_tiles, const float *in, float *out, ssg_stream_t stream);
 int ssg_blindsr_noise(const void *table /* device */, int n_tiles, const float *in, float *out,
                       const float *field /* nullable */, const float *pool /* nullable */, ssg_stream_t stream);
+
+/* ---------------------------------------------------------------- (U) ----
+ * A pixel criterion over a RAGGED SET of tensor pairs, one launch each way: the VGG perceptual loss outside its network
+ * (GAN-Based-SR/basicsr/losses/basic_loss.py:212-251, `percep_loss += criterion(x_features[k], gt_features[k]) *
+ * layer_weights[k]` per tapped layer, and the same over the Gram matrices; train_BSGRAN/models/loss.py:114-130),
+ * ssl_amd/csrc/ssg_mcrit.hip.  Pair k is (x_k, g_k) of n_k >= 1 fp32 elements with the weight w_k; d = x_k[i] - g_k[i].
+ *   kinds  SSG_PIX_L1, SSG_PIX_MSE, SSG_PIX_CHARBONNIER: l and l' of section (R), the same device functions.
+ *          SSG_PIX_FRO (these entry points only): l = d d, the pair's term sqrt(S_k), l' = d.
+ *   ssg_mcrit_sums   S_k = sum_i l(d_i) to sums_out[k], k < n_tensors, and sum_k w_k S_k (FRO: sum_k w_k sqrt(S_k)) to
+ *          sums_out[n_tensors]: n_tensors + 1 DOUBLES ON THE DEVICE.  The caller puts 1 / n_k into w_k for a mean.  One
+ *          launch over the chunks of all pairs (a chunk is ssg_mcrit_chunk() elements of ONE tensor; a workgroup of 256
+ *          threads takes a chunk, and beyond ssg_mcrit_grid_cap() workgroups further chunks grid-stride), one fp64
+ *          partial per chunk in `workspace`, then one launch of one workgroup that folds every tensor's partials in
+ *          chunk order and adds the total in pair order.  Every fp32 l is widened and added in fp64 in a fixed order; no
+ *          atomics.  S_k is the same bits whichever other pairs are in the call, and from call to call.
+ *   ssg_mcrit_grad   grad_k[i] = (float)(c_k (double)l'(d_i)), c_k = coef[0] w_k in fp64; FRO: c_k = coef[0] w_k /
+ *          sqrt(S_k), and 0 where S_k = 0 (torch's norm backward).  coef (ONE DOUBLE) and sums (what ssg_mcrit_sums
+ *          wrote; read for FRO only) are device memory: no host read.  A pair whose grad address is 0 is skipped and
+ *          nothing of it is read or written.  One launch.  With coef[0] w_k formed in fp64, grad_k is ssg_pixel_grad's
+ *          bits on the same pair.
+ * x, g, grad, counts and weights are HOST arrays of n_tensors entries (addresses as size_t).  The records travel in the
+ * kernels' arguments, 16 pairs to a launch; a larger set takes one more launch (of each kind) per 16 pairs.  Inside a
+ * chunk accesses are 16 bytes wide behind a scalar head and in front of a scalar tail wherever g_k or grad_k shares
+ * x_k's alignment mod 16, element by element where it does not: a tensor needs only a float's own alignment.  Stores
+ * stay inside [grad_k, grad_k + n_k).  No allocation, copy, synchronisation or host read.
+ * ssg_mcrit_workspace_bytes: 8 bytes per chunk of the set; 0 where the counts would be refused.
+ * Status, decided before any launch with the outputs untouched: SSG_E_BADARG for a null pointer or array (grad
+ * addresses excepted), n_tensors < 1, n_k = 0, an unknown kind, an eps that is negative or not finite, a NaN weight;
+ * SSG_E_TOOLARGE for a chunk count (of one tensor or of the set) beyond INT_MAX; SSG_E_WORKSPACE for workspace_bytes <
+ * ssg_mcrit_workspace_bytes(); SSG_E_ALIGN for an x, g or grad address that is not 4-byte aligned or a workspace,
+ * sums_out, sums or coef that is not 8-byte aligned. */
+#define SSG_PIX_FRO 3
+int ssg_mcrit_chunk(void);
+int ssg_mcrit_grid_cap(void);
+size_t ssg_mcrit_workspace_bytes(size_t n_tensors, const size_t *counts);
+int ssg_mcrit_sums(size_t n_tensors, const size_t *x, const size_t *g, const size_t *counts, const double *weights,
+                   int kind, float eps, void *workspace, size_t workspace_bytes, double *sums_out /* device */,
+                   ssg_stream_t stream);
+int ssg_mcrit_grad(size_t n_tensors, const size_t *x, const size_t *g, const size_t *grad /* entries nullable */,
+                   const size_t *counts, const double *weights, int kind, float eps, const double *sums /* device */,
+                   const double *coef /* device */, ssg_stream_t stream);
 
 #ifdef SSG_PROFILE
 /* PROFILING BUILD ONLY (libssg_hip_prof.so, compiled with -DSSG_PROFILE; the product library libssg_hip.so does not

@@ -151,6 +151,15 @@ int multi_chunk();
 int multi_grid_cap();
 int launch_multi_apply(const void *table, size_t n_chunks, int kind, float d, float a, const float *w, hipStream_t st);
 
+// ---- ssg_mcrit.hip: a pixel criterion over a ragged set of tensor pairs, one launch each way (entry points beside its
+// kernels) ----
+int mcrit_chunk();
+int mcrit_grid_cap();
+int launch_mcrit_sums(size_t K, const size_t *x, const size_t *g, const size_t *counts, const double *w, int kind,
+                      float eps, void *workspace, double *sums_out, hipStream_t st);
+int launch_mcrit_grad(size_t K, const size_t *x, const size_t *g, const size_t *grad, const size_t *counts,
+                      const double *w, int kind, float eps, const double *sums, const double *coef, hipStream_t st);
+
 // ---- ssg_blindsr.hip: BSRGAN's degradation chain on a ragged batch, one launch per operation family (entry points
 // beside its kernels) ----
 int blindsr_grid_cap();

@@ -43,20 +43,7 @@ struct Planes {
   size_t n;
 };
 
-// l and l' of one difference
-template <int KIND>
-__device__ __forceinline__ float crit(float d, float eps) {
-  if (KIND == SSG_PIX_L1) return fabsf(d);
-  if (KIND == SSG_PIX_MSE) return d * d;
-  return sqrtf(d * d + eps);
-}
-
-template <int KIND>
-__device__ __forceinline__ float dcrit(float d, float eps) {
-  if (KIND == SSG_PIX_L1) return d > 0.f ? 1.f : (d < 0.f ? -1.f : d * 0.f);   // (0 for +-0, NaN for a NaN)
-  if (KIND == SSG_PIX_MSE) return 2.f * d;
-  return d / sqrtf(d * d + eps);
-}
+// (l and l' of one difference, crit<KIND> and dcrit<KIND>, are ssg_stream.hpp's: ssg_mcrit.hip uses the same two)
 
 // (row in its plane, column) of a flat index
 __device__ __forceinline__ void place(const Planes &g, size_t idx, unsigned &i, unsigned &j) {

@@ -1,4 +1,4 @@
-// What the streaming criteria share (ssg_gan.hip, ssg_spsr.hip, and the partial sums of ssg_grow.hip's L1 / KL criteria):
+// What the streaming criteria share (ssg_gan.hip, ssg_spsr.hip, ssg_mcrit.hip, and the partial sums of ssg_grow.hip's L1 / KL criteria):
 // the launch geometry, the walk over a flat fp32 tensor, the fixed-order fp64 sum and the fold of its partials.  One
 // definition each: a fix to the head / tail split or to the order of the sum reaches every file.
 //
@@ -17,6 +17,8 @@
 // pixel::block_sum (ssg_pixel.hpp) is a DIFFERENT sum: it adds the four waves left to right, ((w0 + w1) + w2) + w3, and
 // the files built on it are pinned to those bits.
 #pragma once
+#include <math.h>
+
 #include "ssg_host.hpp"
 
 namespace ssg {
@@ -63,9 +65,25 @@ __device__ __forceinline__ void walk(const float *ptr, size_t n, One one, Quad q
   for (size_t e = head + EPT * n4 + first; e < n; e += stride) one(e);
 }
 
-// NV fp64 partials per workgroup, part[NV * blockIdx.x + k] (every thread must call it)
+// l and l' of one difference d = p - q, every operation fp32 and rounded on its own (the files that use them are
+// compiled with -ffp-contract=off): the pixel criteria of ssg_spsr.hip and ssg_mcrit.hip
+template <int KIND>
+__device__ __forceinline__ float crit(float d, float eps) {
+  if (KIND == SSG_PIX_L1) return fabsf(d);
+  if (KIND == SSG_PIX_MSE) return d * d;
+  return sqrtf(d * d + eps);
+}
+
+template <int KIND>
+__device__ __forceinline__ float dcrit(float d, float eps) {
+  if (KIND == SSG_PIX_L1) return d > 0.f ? 1.f : (d < 0.f ? -1.f : d * 0.f);   // (0 for +-0, NaN for a NaN)
+  if (KIND == SSG_PIX_MSE) return 2.f * d;
+  return d / sqrtf(d * d + eps);
+}
+
+// the workgroup's NV fp64 sums, dst[k] (every thread must call it; a caller that calls it again puts a barrier between)
 template <int NV>
-__device__ __forceinline__ void workgroup_partials(const double (&v)[NV], double *part) {
+__device__ __forceinline__ void workgroup_fold(const double (&v)[NV], double *dst) {
   __shared__ double w[NV][NT / 64];
   double r[NV];
 #pragma unroll
@@ -82,8 +100,14 @@ __device__ __forceinline__ void workgroup_partials(const double (&v)[NV], double
   __syncthreads();
   if (threadIdx.x == 0) {
 #pragma unroll
-    for (int k = 0; k < NV; ++k) part[NV * blockIdx.x + k] = (w[k][0] + w[k][1]) + (w[k][2] + w[k][3]);
+    for (int k = 0; k < NV; ++k) dst[k] = (w[k][0] + w[k][1]) + (w[k][2] + w[k][3]);
   }
+}
+
+// NV fp64 partials per workgroup, part[NV * blockIdx.x + k] (every thread must call it)
+template <int NV>
+__device__ __forceinline__ void workgroup_partials(const double (&v)[NV], double *part) {
+  workgroup_fold<NV>(v, part + NV * blockIdx.x);
 }
 
 // one workgroup folds nparts groups of NV partials into out[0 .. NV)

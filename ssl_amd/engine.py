@@ -1026,3 +1026,92 @@ def pixel_loss(pred, target, kind='mse', eps=1e-12, loss_weight=1.0, reduction='
         pred, target, _scale("pixel_loss", reduction, loss_weight, pred.numel()),
         lambda a, b: _sum_call(a.device, L.ssg_pixel_sums, _ptr(a), _ptr(b), a.numel(), kind, eps),
         lambda a, b, coef, out: _launch(a.device, L.ssg_pixel_grad, _ptr(a), _ptr(b), a.numel(), kind, eps, coef, out))
+
+
+# ------------------------------ a pixel criterion over a ragged set of tensor pairs (ssg_mcrit.hip, section (U)) ----
+MULTI_KINDS = dict(PIXEL_KINDS, fro=_lib.CONSTANTS["SSG_PIX_FRO"])
+
+
+def multi_pair_is_native(pred, target):
+    """Whether the pair can go to the kernels as it lies in memory: fp32 tensors of one non-empty shape on one GPU with
+    equal dense strides (contiguous, channels_last or any other permutation without gaps), so that one flat walk over
+    the memory of both meets corresponding elements."""
+    return (isinstance(pred, torch.Tensor) and isinstance(target, torch.Tensor) and pred.is_cuda
+            and pred.device == target.device and pred.dtype == torch.float32 and target.dtype == torch.float32
+            and pred.shape == target.shape and pred.numel() > 0 and pred.stride() == target.stride()
+            and pred.permute(sorted(range(pred.dim()), key=lambda i: -pred.stride(i))).is_contiguous())
+
+
+def _addresses(values):
+    import numpy as np
+    return np.asarray(values, dtype=np.uintp)
+
+
+class _MultiPixelFn(torch.autograd.Function):
+    """sum_k w_k S_k (fro: sum_k w_k sqrt(S_k)) over K pairs: one ssg_mcrit_sums call (one launch over all chunks and
+    the fold); backward one ssg_mcrit_grad launch that writes the gradient of every pred that wants one.  The pattern
+    of _StreamLossFn, over a list."""
+
+    @staticmethod
+    def forward(ctx, kind, eps, weights, K, *tensors):
+        import numpy as np
+        x = [t.detach() for t in tensors[:K]]
+        g = [t.detach() for t in tensors[K:]]
+        dev = x[0].device
+        L = _lib.lib()
+        px, pg = _addresses([t.data_ptr() for t in x]), _addresses([t.data_ptr() for t in g])
+        counts, w = _addresses([t.numel() for t in x]), np.asarray(weights, dtype=np.float64)
+        sums = torch.empty(K + 1, dtype=torch.float64, device=dev)
+        ws, nbytes = _workspace(L.ssg_mcrit_workspace_bytes(K, counts.ctypes.data), dev)
+        _launch(dev, L.ssg_mcrit_sums, K, px.ctypes.data, pg.ctypes.data, counts.ctypes.data, w.ctypes.data, kind, eps,
+                _ptr(ws), nbytes, _ptr(sums))
+        if any(ctx.needs_input_grad[4:4 + K]):
+            ctx.save_for_backward(sums, *x, *g)
+        ctx.call = (kind, eps, K, px, pg, counts, w)
+        ctx.mark_non_differentiable(sums)
+        return sums[K].to(torch.float32), sums
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gout, _gsums):
+        kind, eps, K, px, pg, counts, w = ctx.call
+        sums, x = ctx.saved_tensors[0], ctx.saved_tensors[1:1 + K]
+        dev = sums.device
+        grads = [torch.empty_like(x[k]) if ctx.needs_input_grad[4 + k] else None for k in range(K)]
+        pgrad = _addresses([0 if t is None else t.data_ptr() for t in grads])
+        _launch(dev, _lib.lib().ssg_mcrit_grad, K, px.ctypes.data, pg.ctypes.data, pgrad.ctypes.data, counts.ctypes.data,
+                w.ctypes.data, kind, eps, _ptr(sums), _ptr(_coef(gout, 1.0, dev)))
+        return (None, None, None, None) + tuple(grads) + (None,) * K
+
+
+def multi_pixel_loss(preds, targets, weights, kind='l1', eps=1e-12, reduction='mean', return_sums=False):
+    """sum_k weights[k] * crit(preds[k], targets[k]) over K pairs of any sizes in one launch each way: kind 'l1' | 'mse' |
+    'charbonnier' (with its eps) under reduction 'mean' (each pair's own mean) | 'sum', or 'fro', the Frobenius norm
+    of each difference (the reduction is not read).  Every pair must satisfy multi_pair_is_native; the gradient goes
+    to each pred that requires it, and targets must not require grad.  return_sums=True returns (loss, the K + 1
+    device doubles S_0 .. S_{K-1}, total)."""
+    if kind not in MULTI_KINDS:
+        raise ValueError(f"ssl_amd: criterion must be one of {sorted(MULTI_KINDS)}, got {kind!r}")
+    eps = float(eps)
+    if not 0.0 <= eps < float("inf"):
+        raise ValueError(f"ssl_amd: eps must be finite and not negative, got {eps!r}")
+    preds, targets, weights = list(preds), list(targets), [float(v) for v in weights]
+    K = len(preds)
+    if K < 1 or len(targets) != K or len(weights) != K:
+        raise ValueError(f"ssl_amd: multi_pixel_loss takes K >= 1 preds, targets and weights, got {K}, {len(targets)} "
+                         f"and {len(weights)}")
+    mean = kind != 'fro' and _reduction_is_mean("multi_pixel_loss", reduction)
+    for p, t in zip(preds, targets):
+        _need_gpu(p, t)
+        if not multi_pair_is_native(p, t):
+            raise ValueError("ssl_amd: multi_pixel_loss takes pairs of fp32 tensors of one non-empty shape with equal "
+                             f"dense strides on one GPU, got {tuple(p.shape)} {p.dtype} {p.stride()} and "
+                             f"{tuple(t.shape)} {t.dtype} {t.stride()}")
+        if p.device != preds[0].device:
+            raise ValueError("ssl_amd: multi_pixel_loss takes the pairs of one GPU")
+        _no_target_grad("multi_pixel_loss", t)
+    if any(v != v for v in weights):
+        raise ValueError("ssl_amd: multi_pixel_loss takes weights that are numbers, got a NaN")
+    scaled = [v / p.numel() if mean else v for v, p in zip(weights, preds)]
+    loss, sums = _MultiPixelFn.apply(MULTI_KINDS[kind], eps, scaled, K, *preds, *targets)
+    return (loss, sums) if return_sums else loss

@@ -5,3 +5,5 @@ from .bebygan import BBL, BackProjectionLoss, BestBuddyLoss, get_flat_mask, imre
 from .ssim import SSIMLoss, create_window, gaussian, ssim  # noqa: F401
 from .gan_loss import GANLoss, MultiScaleGANLoss  # noqa: F401
 from .spsr import CharbonnierLoss, Get_gradient, Get_gradient_nopadding, GradientLoss, MSELoss  # noqa: F401
+from .perceptual import PerceptualLoss, VGGFeatureExtractor  # noqa: F401
+from . import kair  # noqa: F401
