@@ -19,33 +19,24 @@
 //   grads    grad_k[i] = (float)(c_k (double)l'(d_i)), c_k = coef[0] w_k in fp64; FRO: c_k = coef[0] w_k / sqrt(S_k), and
 //            0 where S_k = 0 (torch's norm backward).  coef and S are read on the device.  A pair without a gradient
 //            pointer has no chunk in the launch.
-// A chunk is walked as ssg_stream.hpp walks a tensor: the elements in front of x's first 16-byte boundary and behind the
-// last whole float4 one by one, the rest 16 bytes wide; g and grad 16 bytes wide where they share x's alignment, element
-// by element where they do not.  Every access lies inside the chunk, so inside [p, p + n_k) of its tensor.
+// Chunks, their schedule and their walk are ssg_chunked.hpp's: the walked tensor is x; g and grad are accessed 16 bytes
+// wide where they share x's alignment, element by element where they do not.
 // The pair records travel BY VALUE in the kernel's arguments, MAX_PAIRS to a launch (feature maps move from step to step:
 // a resident table would have to be uploaded every time); a larger set takes further launches into disjoint partial ranges.
 // LDS holds the folds only; no scratch.  The launchers trust their arguments: the entry points below refuse bad ones.
-#include <limits.h>
-
-#include <type_traits>
-
-#include "ssg_stream.hpp"
+#include "ssg_chunked.hpp"
 
 namespace ssg {
 namespace mcrit {
 
-using namespace stream;
+using namespace chunked;
 
 constexpr int CHUNK = 8192;        // elements per chunk: eight float4 trips of a workgroup; the fastest of 4,096, 8,192
                                    // and 16,384 (profiles/perceptual_time.txt)
 constexpr int GRID_CAP = MAX_WG;   // the scaffold's: four workgroups per CU
 constexpr int MAX_PAIRS = 16;      // records per launch: 16 x 56 bytes of kernel arguments
 
-#ifdef SSG_PROFILE
-static int g_chunk = CHUNK, g_grid_cap = GRID_CAP;   // ssg_prof_mcrit_tuning: the A/B of profiles/perceptual_time.txt
-#else
-constexpr int g_chunk = CHUNK, g_grid_cap = GRID_CAP;
-#endif
+SSG_TUNING tuning = {CHUNK, GRID_CAP};   // ssg_prof_mcrit_tuning: the A/B of profiles/perceptual_time.txt
 
 struct Pair {
   const float *x, *g;
@@ -85,28 +76,16 @@ __device__ __forceinline__ float slope(float d, float eps) {
   return dcrit<KIND == SSG_PIX_FRO ? SSG_PIX_MSE : KIND>(d, eps);
 }
 
-// the walk over the len <= chunk elements of one chunk at x: one(e) for an element of the head or the tail, quad(e) for
-// the group e .. e + 3 on a 16-byte boundary of x (head = head_of(x, len), which the caller needs for `wide` as well)
-template <class One, class Quad>
-__device__ __forceinline__ void walk_chunk(unsigned head, unsigned len, One one, Quad quad) {
-  const unsigned t = threadIdx.x, n4 = (len - head) / EPT, tail = head + EPT * n4;
-  if (t < head) one(t);
-  for (unsigned q = t; q < n4; q += NT) quad(head + EPT * q);
-  if (tail + t < len) one(tail + t);
-}
-
 template <int KIND>
 __global__ __launch_bounds__(NT) void mcrit_sums_kernel(const Set s, float eps, double *part) {
   for (unsigned c = blockIdx.x; c < s.n_chunks; c += gridDim.x) {
     const Pair p = pair_of_chunk(s, c);
-    const size_t off = (size_t)(c - p.first) * s.chunk;
-    const unsigned len = p.n - off < s.chunk ? (unsigned)(p.n - off) : s.chunk;
-    const float *x = p.x + off, *g = p.g + off;
-    const unsigned head = (unsigned)head_of(x, len);
-    const bool gv = wide(g, head);
+    const Span sp = span_of(p.n, c - p.first, s.chunk);
+    const float *x = p.x + sp.off, *g = p.g + sp.off;
+    const bool gv = wide(g, head_of(x, sp.len));
     double L = 0.0;
     walk_chunk(
-        head, len, [&](unsigned e) { L += (double)value<KIND>(x[e] - g[e], eps); },
+        x, sp.len, [&](unsigned e) { L += (double)value<KIND>(x[e] - g[e], eps); },
         [&](unsigned e) {
           float a[4], b[4];
           load4(x + e, true, a);
@@ -156,14 +135,13 @@ __global__ __launch_bounds__(NT) void mcrit_grad_kernel(const Set s, float eps, 
       const double Sk = S[p.index];
       ck = Sk == 0.0 ? 0.0 : ck / sqrt(Sk);
     }
-    const size_t off = (size_t)(c - p.first) * s.chunk;
-    const unsigned len = p.n - off < s.chunk ? (unsigned)(p.n - off) : s.chunk;
-    const float *x = p.x + off, *g = p.g + off;
-    float *out = p.grad + off;
-    const unsigned head = (unsigned)head_of(x, len);
+    const Span sp = span_of(p.n, c - p.first, s.chunk);
+    const float *x = p.x + sp.off, *g = p.g + sp.off;
+    float *out = p.grad + sp.off;
+    const size_t head = head_of(x, sp.len);
     const bool gv = wide(g, head), ov = wide(out, head);
     walk_chunk(
-        head, len, [&](unsigned e) { out[e] = (float)(ck * (double)slope<KIND>(x[e] - g[e], eps)); },
+        x, sp.len, [&](unsigned e) { out[e] = (float)(ck * (double)slope<KIND>(x[e] - g[e], eps)); },
         [&](unsigned e) {
           float a[4], b[4], r[4];
           load4(x + e, true, a);
@@ -175,37 +153,13 @@ __global__ __launch_bounds__(NT) void mcrit_grad_kernel(const Set s, float eps, 
 }
 
 // ---- host ----
-template <class F>
-inline void with_kind(int kind, F f) {
-  switch (kind) {
-    case SSG_PIX_L1: f(std::integral_constant<int, SSG_PIX_L1>{}); break;
-    case SSG_PIX_MSE: f(std::integral_constant<int, SSG_PIX_MSE>{}); break;
-    case SSG_PIX_CHARBONNIER: f(std::integral_constant<int, SSG_PIX_CHARBONNIER>{}); break;
-    default: f(std::integral_constant<int, SSG_PIX_FRO>{}); break;
-  }
-}
-
-inline size_t chunks_of(size_t n, size_t chunk) { return n / chunk + (n % chunk != 0); }
-
-// the number of chunks of a set; false where a tensor's or the set's count does not fit an int (SSG_E_TOOLARGE)
-static bool count_chunks(size_t K, const size_t *counts, size_t chunk, size_t *total) {
-  size_t sum = 0;
-  for (size_t k = 0; k < K; ++k) {
-    const size_t c = chunks_of(counts[k], chunk);
-    if (c > (size_t)INT_MAX || sum + c > (size_t)INT_MAX) return false;
-    sum += c;
-  }
-  *total = sum;
-  return true;
-}
-
 // Cuts the pairs k with keep(k) into launches of at most MAX_PAIRS records and calls go(set, first chunk of the launch
 // among the kept pairs' chunks, whether it is the first launch); stops at the first status that is not 0.
 template <class Keep, class Go>
 inline int for_each_launch(size_t K, const size_t *x, const size_t *g, const size_t *grad, const size_t *counts,
                            const double *w, Keep keep, Go go) {
   Set s;
-  s.K = 0, s.n_chunks = 0, s.chunk = (unsigned)g_chunk;
+  s.K = 0, s.n_chunks = 0, s.chunk = (unsigned)tuning.chunk;
   size_t base = 0;
   bool first = true;
   for (size_t k = 0; k <= K; ++k) {
@@ -226,8 +180,6 @@ inline int for_each_launch(size_t K, const size_t *x, const size_t *g, const siz
   return 0;
 }
 
-inline unsigned grid_of(const Set &s) { return s.n_chunks < (unsigned)g_grid_cap ? s.n_chunks : (unsigned)g_grid_cap; }
-
 inline bool unaligned(size_t p, size_t a) { return p % a != 0; }
 
 // what the two entry points check of the pairs; `grad` may be null (the sums call) and may hold null addresses
@@ -239,7 +191,7 @@ static int check_pairs(size_t K, const size_t *x, const size_t *g, const size_t 
   for (size_t k = 0; k < K; ++k) {
     if (!x[k] || !g[k] || counts[k] == 0 || w[k] != w[k]) return SSG_E_BADARG;
   }
-  if (!count_chunks(K, counts, (size_t)g_chunk, total)) return SSG_E_TOOLARGE;
+  if (!count_chunks(K, counts, (size_t)tuning.chunk, total)) return SSG_E_TOOLARGE;
   for (size_t k = 0; k < K; ++k) {
     if (unaligned(x[k], 4) || unaligned(g[k], 4) || (grad && unaligned(grad[k], 4))) return SSG_E_ALIGN;
   }
@@ -248,9 +200,9 @@ static int check_pairs(size_t K, const size_t *x, const size_t *g, const size_t 
 
 }  // namespace mcrit
 
-int mcrit_chunk() { return mcrit::g_chunk; }
+int mcrit_chunk() { return mcrit::tuning.chunk; }
 
-int mcrit_grid_cap() { return mcrit::g_grid_cap; }
+int mcrit_grid_cap() { return mcrit::tuning.grid_cap; }
 
 int launch_mcrit_sums(size_t K, const size_t *x, const size_t *g, const size_t *counts, const double *w, int kind,
                       float eps, void *workspace, double *sums_out, hipStream_t st) {
@@ -259,8 +211,9 @@ int launch_mcrit_sums(size_t K, const size_t *x, const size_t *g, const size_t *
       K, x, g, nullptr, counts, w, [](size_t) { return true; },
       [&](const Set &s, size_t base, bool first) {
         double *part = (double *)workspace + base;
-        with_kind(kind, [&](auto kd) {
-          hipLaunchKernelGGL(mcrit_sums_kernel<decltype(kd)::value>, dim3(grid_of(s)), dim3(NT), 0, st, s, eps, part);
+        with_pixel_kind<true>(kind, [&](auto kd) {
+          hipLaunchKernelGGL(mcrit_sums_kernel<decltype(kd)::value>, dim3(grid_of(s.n_chunks, tuning)), dim3(NT), 0, st,
+                             s, eps, part);
         });
         hipLaunchKernelGGL(mcrit_fold_kernel, dim3(1), dim3(NT), 0, st, s, (int)(kind == SSG_PIX_FRO), (int)!first,
                            (const double *)part, sums_out, (int)K);
@@ -274,9 +227,9 @@ int launch_mcrit_grad(size_t K, const size_t *x, const size_t *g, const size_t *
   return for_each_launch(
       K, x, g, grad, counts, w, [&](size_t k) { return grad[k] != 0; },
       [&](const Set &s, size_t, bool) {
-        with_kind(kind, [&](auto kd) {
-          hipLaunchKernelGGL(mcrit_grad_kernel<decltype(kd)::value>, dim3(grid_of(s)), dim3(NT), 0, st, s, eps, coef,
-                             sums);
+        with_pixel_kind<true>(kind, [&](auto kd) {
+          hipLaunchKernelGGL(mcrit_grad_kernel<decltype(kd)::value>, dim3(grid_of(s.n_chunks, tuning)), dim3(NT), 0, st,
+                             s, eps, coef, sums);
         });
         return (int)hipGetLastError();
       });
@@ -326,9 +279,7 @@ int ssg_mcrit_grad(size_t n_tensors, const size_t *x, const size_t *g, const siz
 // multiple of 4) and grid cap that ssg_mcrit_chunk / ssg_mcrit_grid_cap, and so the workspaces sized and the launches
 // made afterwards, use: the A/B of profiles/perceptual_time.txt.  The product library's two are constants.
 int ssg_prof_mcrit_tuning(int chunk, int grid_cap) {
-  if (chunk < 4 || chunk % 4 || grid_cap < 1) return SSG_E_BADARG;
-  mcrit::g_chunk = chunk, mcrit::g_grid_cap = grid_cap;
-  return 0;
+  return mcrit::tuning.set(chunk, grid_cap);
 }
 #endif
 

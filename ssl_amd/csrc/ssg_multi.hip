@@ -14,24 +14,18 @@
 //   [0] n_tensors  [1] n_chunks  [2] chunk (elements)  [3] 0
 //   n_tensors records of three words   dst address, src address, n (elements)
 //   n_chunks words                     tensor index << 32 | index of the chunk inside that tensor
-// in tensor order and, inside a tensor, in chunk order; an empty tensor has a record and no chunk.  A workgroup of 256
-// threads takes chunk c = blockIdx.x, then c + gridDim.x, ... (at most ssg_multi_grid_cap() workgroups).  The chunk
-// covers elements [k chunk, min(n, (k + 1) chunk)) of its tensor; it is walked as ssg_stream.hpp walks a tensor: the
-// elements in front of dst's first 16-byte boundary and behind the last whole float4 one by one, the rest 16 bytes wide
-// where src shares dst's alignment, element by element where it does not.  Every store lies inside the chunk, so inside
-// [dst, dst + n) of its tensor.  A chunk word that points outside the table's own tensors or past a tensor's end is
-// skipped.  No LDS, no atomics, no scratch.
+// in tensor order and, inside a tensor, in chunk order; an empty tensor has a record and no chunk.  Chunks, their
+// schedule (at most ssg_multi_grid_cap() workgroups) and their walk are ssg_chunked.hpp's: the walked tensor is dst,
+// always accessed 16 bytes wide between its head and tail; src is read 16 bytes wide where it shares dst's alignment
+// and element by element where it does not.  A chunk word that points outside the table's own tensors or past a
+// tensor's end is skipped.  No LDS, no atomics, no scratch.
 // The launcher trusts its arguments: ssg_multi_apply below refuses bad ones before the launch.
-#include <limits.h>
-
-#include <type_traits>
-
-#include "ssg_stream.hpp"
+#include "ssg_chunked.hpp"
 
 namespace ssg {
 namespace multi {
 
-using namespace stream;
+using namespace chunked;
 
 typedef unsigned long long word;
 
@@ -39,11 +33,7 @@ constexpr int CHUNK = 4096;       // elements per chunk: four float4 trips of a 
 constexpr int GRID_CAP = MAX_WG;  // the scaffold's: four workgroups per CU
 constexpr size_t HEADER_WORDS = 4, RECORD_WORDS = 3;
 
-#ifdef SSG_PROFILE
-static int g_chunk = CHUNK, g_grid_cap = GRID_CAP;   // ssg_prof_multi_tuning: the A/B of profiles/ema_time.txt
-#else
-constexpr int g_chunk = CHUNK, g_grid_cap = GRID_CAP;
-#endif
+SSG_TUNING tuning = {CHUNK, GRID_CAP};   // ssg_prof_multi_tuning: the A/B of profiles/ema_time.txt
 
 template <int KIND>
 __device__ __forceinline__ float updated(float e, float p, float d, float a) {
@@ -62,61 +52,46 @@ __global__ __launch_bounds__(NT) void multi_kernel(const word *table, float d, f
   const unsigned chunk = (unsigned)table[2];
   const word *records = table + HEADER_WORDS, *chunks = records + RECORD_WORDS * n_tensors;
   if (KIND == SSG_MT_LIT) a = w[0];
-  const unsigned t = threadIdx.x;
   for (word c = blockIdx.x; c < n_chunks; c += gridDim.x) {
     const word cw = chunks[c], ti = cw >> 32;
     if (ti >= n_tensors) continue;
     const word *rec = records + RECORD_WORDS * ti;
-    const size_t n = (size_t)rec[2], off = (size_t)(cw & 0xffffffffull) * chunk;
-    if (off >= n) continue;
-    const unsigned len = n - off < chunk ? (unsigned)(n - off) : chunk;
-    float *e = (float *)rec[0] + off;
-    const float *p = (const float *)rec[1] + off;
-    const auto one = [&](unsigned i) { e[i] = updated<KIND>(KIND == SSG_MT_COPY ? 0.f : e[i], p[i], d, a); };
-    const unsigned head = (unsigned)head_of(e, len);
-    if (wide(p, head)) {
-      const unsigned n4 = (len - head) / EPT, tail = head + EPT * n4;
-      if (t < head) one(t);
-      for (unsigned q = t; q < n4; q += NT) {
-        float ve[4] = {0.f, 0.f, 0.f, 0.f}, vp[4], r[4];
-        if (KIND != SSG_MT_COPY) load4(e + head + EPT * q, true, ve);
-        load4(p + head + EPT * q, true, vp);
+    const Span sp = span_of((size_t)rec[2], (size_t)(cw & 0xffffffffull), chunk);
+    if (sp.off >= (size_t)rec[2]) continue;
+    float *e = (float *)rec[0] + sp.off;
+    const float *p = (const float *)rec[1] + sp.off;
+    // (the chunk's one decision is taken in front of the walk: with `wide` inside the group function the compiler
+    // merges load4's two forms into a 12-byte and a 4-byte load for both, which costs the aligned set 3 %)
+    const auto walk_with = [&](auto pv) {
+      walk_chunk(
+          e, sp.len, [&](unsigned i) { e[i] = updated<KIND>(KIND == SSG_MT_COPY ? 0.f : e[i], p[i], d, a); },
+          [&](unsigned i) {
+            float ve[4] = {0.f, 0.f, 0.f, 0.f}, vp[4], r[4];
+            if (KIND != SSG_MT_COPY) load4(e + i, true, ve);
+            load4(p + i, decltype(pv)::value, vp);
 #pragma unroll
-        for (int k = 0; k < 4; ++k) r[k] = updated<KIND>(ve[k], vp[k], d, a);
-        store4(e + head + EPT * q, true, r);
-      }
-      if (tail + t < len) one(tail + t);
-    } else {
-      for (unsigned i = t; i < len; i += NT) one(i);
-    }
+            for (int k = 0; k < 4; ++k) r[k] = updated<KIND>(ve[k], vp[k], d, a);
+            store4(e + i, true, r);
+          });
+    };
+    if (wide(p, head_of(e, sp.len))) walk_with(std::true_type{});
+    else walk_with(std::false_type{});
   }
-}
-
-// the number of chunks of a set; false where a tensor's or the set's count does not fit (SSG_E_TOOLARGE)
-static bool count_chunks(size_t n_tensors, const size_t *counts, size_t chunk, size_t *total) {
-  size_t sum = 0;
-  for (size_t i = 0; i < n_tensors; ++i) {
-    const size_t c = counts[i] / chunk + (counts[i] % chunk != 0);
-    if (c > (size_t)INT_MAX || sum + c > (size_t)INT_MAX) return false;
-    sum += c;
-  }
-  *total = sum;
-  return true;
 }
 
 static size_t table_words(size_t n_tensors, size_t n_chunks) { return HEADER_WORDS + RECORD_WORDS * n_tensors + n_chunks; }
 
 }  // namespace multi
 
-int multi_chunk() { return multi::g_chunk; }
+int multi_chunk() { return multi::tuning.chunk; }
 
-int multi_grid_cap() { return multi::g_grid_cap; }
+int multi_grid_cap() { return multi::tuning.grid_cap; }
 
 int launch_multi_apply(const void *table, size_t n_chunks, int kind, float d, float a, const float *w, hipStream_t st) {
   using namespace multi;
-  const unsigned grid = (unsigned)(n_chunks < (size_t)g_grid_cap ? n_chunks : (size_t)g_grid_cap);
   const auto go = [&](auto k) {
-    hipLaunchKernelGGL(multi_kernel<decltype(k)::value>, dim3(grid), dim3(NT), 0, st, (const word *)table, d, a, w);
+    hipLaunchKernelGGL(multi_kernel<decltype(k)::value>, dim3(grid_of(n_chunks, tuning)), dim3(NT), 0, st,
+                       (const word *)table, d, a, w);
   };
   if (kind == SSG_MT_EMA) go(std::integral_constant<int, SSG_MT_EMA>{});
   else if (kind == SSG_MT_LIT) go(std::integral_constant<int, SSG_MT_LIT>{});
@@ -188,9 +163,7 @@ int ssg_multi_apply(const void *table, size_t n_chunks, int kind, float d, float
 // 4) and grid cap that ssg_multi_chunk / ssg_multi_grid_cap, and so the tables filled and the launches made afterwards,
 // use: the A/B of profiles/ema_time.txt.  The product library's two are constants.
 int ssg_prof_multi_tuning(int chunk, int grid_cap) {
-  if (chunk < 4 || chunk % 4 || grid_cap < 1) return SSG_E_BADARG;
-  multi::g_chunk = chunk, multi::g_grid_cap = grid_cap;
-  return 0;
+  return multi::tuning.set(chunk, grid_cap);
 }
 #endif
 

@@ -25,10 +25,6 @@
 // kernels read their distance-2 neighbourhood element by element from L1 / L2 (lanes are consecutive: coalesced).
 // A plane's results do not depend on the planes around it: plane p of a batch is the same bits as the plane alone.
 // The launchers trust their arguments: the entry points in ssg_api.hip refuse bad ones before any launch.
-#include <math.h>
-
-#include <type_traits>
-
 #include "ssg_stream.hpp"
 
 namespace ssg {
@@ -245,16 +241,6 @@ __global__ __launch_bounds__(NT) void pixel_grad_kernel(const float *a, const fl
       });
 }
 
-// the family's kinds, spelled out once: f(std::integral_constant<int, KIND>)
-template <class F>
-inline void with_kind(int kind, F f) {
-  switch (kind) {
-    case SSG_PIX_L1: f(std::integral_constant<int, SSG_PIX_L1>{}); break;
-    case SSG_PIX_MSE: f(std::integral_constant<int, SSG_PIX_MSE>{}); break;
-    default: f(std::integral_constant<int, SSG_PIX_CHARBONNIER>{}); break;
-  }
-}
-
 inline Planes planes_of(int planes, int H, int W) { return Planes{(unsigned)H, (unsigned)W, (size_t)planes * H * W}; }
 
 }  // namespace spsr
@@ -276,7 +262,7 @@ int launch_spsr_loss(const float *x, const float *t, int planes, int H, int W, i
   const Planes g = planes_of(planes, H, W);
   const unsigned grid = grid_for(g.n, EPT);
   double *part = partials_of(grid, workspace, sum_out);
-  with_kind(kind, [&](auto k) {
+  with_pixel_kind(kind, [&](auto k) {
     hipLaunchKernelGGL(spsr_loss_kernel<decltype(k)::value>, dim3(grid), dim3(NT), 0, st, x, t, g, eps, map_out, part);
   });
   return finish_sums<1>(grid, part, sum_out, st);
@@ -290,7 +276,7 @@ int launch_spsr_gather(const float *x, const float *t, const float *gmap, const 
   if (!t) {
     hipLaunchKernelGGL((spsr_gather_kernel<SSG_PIX_L1, false>), dim3(grid), dim3(NT), 0, st, x, t, gmap, coef, g, eps, dx);
   } else {
-    with_kind(kind, [&](auto k) {
+    with_pixel_kind(kind, [&](auto k) {
       hipLaunchKernelGGL((spsr_gather_kernel<decltype(k)::value, true>), dim3(grid), dim3(NT), 0, st, x, t, gmap, coef, g,
                          eps, dx);
     });
@@ -304,7 +290,7 @@ int launch_spsr_branch_sums(const float *branch, const float *gt, int planes, in
   const Planes g = planes_of(planes, H, W);
   const unsigned grid = grid_for(g.n, EPT);
   double *part = partials_of(grid, workspace, sum_out);
-  with_kind(kind, [&](auto k) {
+  with_pixel_kind(kind, [&](auto k) {
     hipLaunchKernelGGL(spsr_branch_sums_kernel<decltype(k)::value>, dim3(grid), dim3(NT), 0, st, branch, gt, g, eps, part);
   });
   return finish_sums<1>(grid, part, sum_out, st);
@@ -314,7 +300,7 @@ int launch_spsr_branch_grad(const float *branch, const float *gt, int planes, in
                             const double *coef, float *grad, hipStream_t st) {
   using namespace spsr;
   const Planes g = planes_of(planes, H, W);
-  with_kind(kind, [&](auto k) {
+  with_pixel_kind(kind, [&](auto k) {
     hipLaunchKernelGGL(spsr_branch_grad_kernel<decltype(k)::value>, dim3(grid_for(g.n, EPT)), dim3(NT), 0, st, branch, gt,
                        g, eps, coef, grad);
   });
@@ -326,7 +312,7 @@ int launch_pixel_sums(const float *a, const float *b, size_t n, int kind, float 
   using namespace spsr;
   const unsigned grid = grid_for(n, EPT);
   double *part = partials_of(grid, workspace, sum_out);
-  with_kind(kind, [&](auto k) {
+  with_pixel_kind(kind, [&](auto k) {
     hipLaunchKernelGGL(pixel_sums_kernel<decltype(k)::value>, dim3(grid), dim3(NT), 0, st, a, b, n, eps, part);
   });
   return finish_sums<1>(grid, part, sum_out, st);
@@ -335,7 +321,7 @@ int launch_pixel_sums(const float *a, const float *b, size_t n, int kind, float 
 int launch_pixel_grad(const float *a, const float *b, size_t n, int kind, float eps, const double *coef, float *grad,
                       hipStream_t st) {
   using namespace spsr;
-  with_kind(kind, [&](auto k) {
+  with_pixel_kind(kind, [&](auto k) {
     hipLaunchKernelGGL(pixel_grad_kernel<decltype(k)::value>, dim3(grid_for(n, EPT)), dim3(NT), 0, st, a, b, n, eps, coef,
                        grad);
   });

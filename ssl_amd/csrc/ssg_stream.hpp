@@ -8,7 +8,8 @@
 //           4-byte aligned is served at full width.  One group of four per thread and trip; a grid is one workgroup per
 //           1,024 elements, at most MAX_WG of them; beyond MAX_WG * 1,024 elements a workgroup walks (grid-stride).  Any
 //           other tensor of the call is accessed 16 bytes wide where it shares the walked tensor's alignment (`wide`)
-//           and element by element where it does not.
+//           and element by element where it does not.  walk_span is the one spelling of this: `walk` is it for the
+//           grid over a tensor, ssg_chunked.hpp's walk_chunk for a workgroup over one chunk of a ragged set.
 //   sums    each fp32 value is widened and ADDED IN FP64.  A thread adds its elements in index order, a wave folds by
 //           the shuffle tree, a workgroup adds its four waves in order, pairwise: (w0 + w1) + (w2 + w3); one workgroup
 //           folds the partials (thread i takes i, i + 256, ..., then an LDS tree).  No atomics, no tickets: the same
@@ -18,6 +19,8 @@
 // the files built on it are pinned to those bits.
 #pragma once
 #include <math.h>
+
+#include <type_traits>
 
 #include "ssg_host.hpp"
 
@@ -54,15 +57,22 @@ __device__ __forceinline__ void store4(float *p, bool vec, const float o[4]) {
   }
 }
 
-// the flat walk over the n elements behind ptr: one(e) for an element of the head or the tail, quad(e) for the group
-// e .. e + 3, whose first element lies on a 16-byte boundary
+// THE walk, of which every other is a case: the span of n elements whose first `head` lie in front of a 16-byte boundary,
+// for the threads first, first + stride, ...  A thread meets its elements in this order: one(e) for its element of the
+// head, quad(e) for its groups e .. e + 3 (on a 16-byte boundary) in ascending order, one(e) for its element of the tail
+// behind the last whole group.  I is the index type: size_t for a tensor, unsigned inside a chunk.
+template <class I, class One, class Quad>
+__device__ __forceinline__ void walk_span(I head, I n, I first, I stride, One one, Quad quad) {
+  const I n4 = (n - head) / EPT;
+  for (I e = first; e < head; e += stride) one(e);
+  for (I q = first; q < n4; q += stride) quad(head + EPT * q);
+  for (I e = head + EPT * n4 + first; e < n; e += stride) one(e);
+}
+
+// the flat walk of the whole grid over the n elements behind ptr (grid-stride)
 template <class One, class Quad>
 __device__ __forceinline__ void walk(const float *ptr, size_t n, One one, Quad quad) {
-  const size_t head = head_of(ptr, n), n4 = (n - head) / EPT;
-  const size_t first = (size_t)blockIdx.x * NT + threadIdx.x, stride = (size_t)gridDim.x * NT;
-  for (size_t e = first; e < head; e += stride) one(e);
-  for (size_t q = first; q < n4; q += stride) quad(head + EPT * q);
-  for (size_t e = head + EPT * n4 + first; e < n; e += stride) one(e);
+  walk_span<size_t>(head_of(ptr, n), n, (size_t)blockIdx.x * NT + threadIdx.x, (size_t)gridDim.x * NT, one, quad);
 }
 
 // l and l' of one difference d = p - q, every operation fp32 and rounded on its own (the files that use them are
@@ -138,6 +148,16 @@ __global__ __launch_bounds__(NT) void fold_kernel(const double *part, int nparts
 }
 
 // ---- host ----
+// the pixel kinds, spelled out once: f(std::integral_constant<int, KIND>).  SSG_PIX_FRO is ssg_mcrit.hip's extra kind;
+// without FRO no kernel of it is instantiated
+template <bool FRO = false, class F>
+inline void with_pixel_kind(int kind, F f) {
+  if (kind == SSG_PIX_L1) f(std::integral_constant<int, SSG_PIX_L1>{});
+  else if (kind == SSG_PIX_MSE) f(std::integral_constant<int, SSG_PIX_MSE>{});
+  else if (FRO && kind == SSG_PIX_FRO) f(std::integral_constant<int, FRO ? SSG_PIX_FRO : SSG_PIX_CHARBONNIER>{});
+  else f(std::integral_constant<int, SSG_PIX_CHARBONNIER>{});
+}
+
 inline unsigned grid_for(size_t n, int per_thread) {
   const size_t per = (size_t)NT * per_thread, want = (n + per - 1) / per;
   return (unsigned)(want < 1 ? 1 : (want > MAX_WG ? MAX_WG : want));

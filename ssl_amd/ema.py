@@ -30,12 +30,13 @@ import contextlib
 import operator
 import weakref
 
-import numpy as np
 import torch
 from torch import nn
 from torch.nn.parallel import DataParallel, DistributedDataParallel
 
 from . import _lib
+from .engine import address_array
+from .engine import dense_strides as _dense
 from .losses import basic_loss
 from .losses.gan_loss import _RAW_STREAM
 from .losses.gan_loss import _on as _on_cuda
@@ -84,16 +85,6 @@ def _stream(device):
     return _RAW_STREAM(device.index) if _RAW_STREAM else torch.cuda.current_stream().cuda_stream
 
 
-def _dense(t):
-    """Non-overlapping and dense: the strides are those of some permutation of a contiguous layout."""
-    expect = 1
-    for stride, size in sorted((st, sz) for sz, st in zip(t.shape, t.stride()) if sz != 1):
-        if stride != expect:
-            return False
-        expect *= size
-    return True
-
-
 def _native_pair(e, p):
     if not (_on_gpu(e) and _on_gpu(p) and e.device == p.device and e.dtype == torch.float32 and p.dtype == torch.float32
             and e.shape == p.shape and e.stride() == p.stride() and _dense(e)):
@@ -125,7 +116,7 @@ def _pairs_overlap(pairs):
 def build_table(dst_ptrs, src_ptrs, counts, device):
     """(the table on `device`, its chunk count, the host image) for host lists of addresses and element counts."""
     L = _library()
-    d, s, c = (np.ascontiguousarray(v, dtype=np.uintp) for v in (dst_ptrs, src_ptrs, counts))
+    d, s, c = (address_array(v) for v in (dst_ptrs, src_ptrs, counts))
     n = len(c)
     nbytes = L.ssg_multi_table_bytes(n, c.ctypes.data)
     if nbytes == 0:

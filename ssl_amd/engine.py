@@ -1032,19 +1032,32 @@ def pixel_loss(pred, target, kind='mse', eps=1e-12, loss_weight=1.0, reduction='
 MULTI_KINDS = dict(PIXEL_KINDS, fro=_lib.CONSTANTS["SSG_PIX_FRO"])
 
 
+def dense_strides(t):
+    """Non-overlapping and dense: the strides are those of some permutation of a contiguous layout (contiguous,
+    channels_last, any other permutation without gaps), so that one flat walk over the memory of two such tensors of
+    equal strides meets corresponding elements.  Dimensions of size 1 do not count, whatever their strides.  The one
+    spelling of this for the ragged kernels' callers (multi_pair_is_native here, ssl_amd/ema.py)."""
+    expect = 1
+    for stride, size in sorted((st, sz) for sz, st in zip(t.shape, t.stride()) if sz != 1):
+        if stride != expect:
+            return False
+        expect *= size
+    return True
+
+
+def address_array(values):
+    """Host addresses or element counts as the size_t array that the ragged entry points take (pass .ctypes.data)."""
+    import numpy as np
+    return np.ascontiguousarray(values, dtype=np.uintp)
+
+
 def multi_pair_is_native(pred, target):
     """Whether the pair can go to the kernels as it lies in memory: fp32 tensors of one non-empty shape on one GPU with
-    equal dense strides (contiguous, channels_last or any other permutation without gaps), so that one flat walk over
-    the memory of both meets corresponding elements."""
+    equal dense strides (dense_strides)."""
     return (isinstance(pred, torch.Tensor) and isinstance(target, torch.Tensor) and pred.is_cuda
             and pred.device == target.device and pred.dtype == torch.float32 and target.dtype == torch.float32
             and pred.shape == target.shape and pred.numel() > 0 and pred.stride() == target.stride()
-            and pred.permute(sorted(range(pred.dim()), key=lambda i: -pred.stride(i))).is_contiguous())
-
-
-def _addresses(values):
-    import numpy as np
-    return np.asarray(values, dtype=np.uintp)
+            and dense_strides(pred))
 
 
 class _MultiPixelFn(torch.autograd.Function):
@@ -1059,8 +1072,8 @@ class _MultiPixelFn(torch.autograd.Function):
         g = [t.detach() for t in tensors[K:]]
         dev = x[0].device
         L = _lib.lib()
-        px, pg = _addresses([t.data_ptr() for t in x]), _addresses([t.data_ptr() for t in g])
-        counts, w = _addresses([t.numel() for t in x]), np.asarray(weights, dtype=np.float64)
+        px, pg = address_array([t.data_ptr() for t in x]), address_array([t.data_ptr() for t in g])
+        counts, w = address_array([t.numel() for t in x]), np.asarray(weights, dtype=np.float64)
         sums = torch.empty(K + 1, dtype=torch.float64, device=dev)
         ws, nbytes = _workspace(L.ssg_mcrit_workspace_bytes(K, counts.ctypes.data), dev)
         _launch(dev, L.ssg_mcrit_sums, K, px.ctypes.data, pg.ctypes.data, counts.ctypes.data, w.ctypes.data, kind, eps,
@@ -1078,7 +1091,7 @@ class _MultiPixelFn(torch.autograd.Function):
         sums, x = ctx.saved_tensors[0], ctx.saved_tensors[1:1 + K]
         dev = sums.device
         grads = [torch.empty_like(x[k]) if ctx.needs_input_grad[4 + k] else None for k in range(K)]
-        pgrad = _addresses([0 if t is None else t.data_ptr() for t in grads])
+        pgrad = address_array([0 if t is None else t.data_ptr() for t in grads])
         _launch(dev, _lib.lib().ssg_mcrit_grad, K, px.ctypes.data, pg.ctypes.data, pgrad.ctypes.data, counts.ctypes.data,
                 w.ctypes.data, kind, eps, _ptr(sums), _ptr(_coef(gout, 1.0, dev)))
         return (None, None, None, None) + tuple(grads) + (None,) * K

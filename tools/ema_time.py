@@ -146,6 +146,24 @@ def main():
         if name != "native":
             rec.update(over_native=round(med / res["native"][0], 2))
         record(lines, **rec)
+    # (d) again on the same set with every src ONE FLOAT past dst's alignment: dst is still stored 16 bytes wide, src is
+    # read element by element (the pairs of a view into a flat buffer)
+    pos, offs = 0, []
+    for p in ps:
+        pos = -(-pos // 4) * 4 + 1
+        offs.append(pos)
+        pos += p.numel()
+    buf = torch.randn(pos, device=dev) * 0.05
+    t1, nc1, _host1 = ema.build_table([e.data_ptr() for e in es], [buf.data_ptr() + 4 * o for o in offs],
+                                      [e.numel() for e in es], dev)
+
+    def c_call_src_off1():
+        _lib.check(L.ssg_multi_apply(t1.data_ptr(), nc1, ema.EMA, d, a, None, stream))
+
+    res1 = compare([("c_call", c_call), ("c_call_src_off1", c_call_src_off1)], args.iters, args.rounds, args.warmup)
+    for name, (med, lo, hi, _) in res1.items():
+        record(lines, set="rrdbnet, src off by one float", path=name, ms_median=round(med, 4), ms_min=round(lo, 4),
+               ms_max=round(hi, 4), windows=args.rounds, iters=args.iters, floor_share=round(floor_ms / med, 4))
     # the host time of the per-call validation alone
     flat = m.dst + m.src
     checks = []
