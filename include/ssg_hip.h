@@ -78,6 +78,8 @@ typedef void *ssg_stream_t; /* hipStream_t */
  * ssg_multi_grid_cap (the EMA and copy updates of a parameter set in one launch, section (S)). */
 /* 6, additive: + ssg_mcrit_sums, ssg_mcrit_grad, ssg_mcrit_workspace_bytes, ssg_mcrit_chunk, ssg_mcrit_grid_cap and
  * SSG_PIX_FRO (a pixel criterion over a ragged set of tensor pairs: the perceptual loss, section (U)). */
+/* 6, additive: + ssg_lpips_layers, ssg_dists_score, ssg_lpips_workspace_bytes, ssg_dists_workspace_bytes,
+ * ssg_featmetric_grid_cap / _unit / _chunk (the LPIPS and DISTS criteria over their feature pairs, section (V)). */
 int ssg_abi_version(void);
 const char *ssg_status_string(int status);
 /* Device-side refusals that no return value can carry (everything is asynchronous): waits for `stream`, then returns
@@ -1175,6 +1177,47 @@ int ssg_mcrit_sums(size_t n_tensors, const size_t *x, const size_t *g, const siz
 int ssg_mcrit_grad(size_t n_tensors, const size_t *x, const size_t *g, const size_t *grad /* entries nullable */,
                    const size_t *counts, const double *weights, int kind, float eps, const double *sums /* device */,
                    const double *coef /* device */, ssg_stream_t stream);
+
+/* ---------------------------------------------------------------- (V) ----
+ * The criteria of the LPIPS (v0.1) and DISTS validation metrics outside their networks, over a RAGGED SET of feature
+ * pairs in one launch each plus one finishing launch, ssl_amd/csrc/ssg_featmetric.hip.  Layer k holds n_images fp32
+ * NCHW contiguous maps of (C[k], H[k], W[k]) on either side; a map needs only a float's alignment.  Every sum is fp64, of
+ * products of two fp32 factors formed in fp64, in a fixed order: no atomics, no scratch, one partial per work unit in
+ * `workspace`, folded in unit order.  Results are the same bits from call to call; image n of a batch gives the bits of
+ * the image alone; a layer's partials are the same bits whichever other layers are in the call.
+ *   ssg_lpips_layers   per pixel d = sum_c w_c (f0_c / (n0 + 1e-10) - f1_c / (n1 + 1e-10))^2, n = sqrt(sum_c f_c^2), formed
+ *          in ONE pass over the channels as A i0^2 - 2 B i0 i1 + Cc i1^2 (A = sum w f0^2, B = sum w f0 f1, Cc = sum w f1^2,
+ *          i = 1 / (n + 1e-10)) in fp64, 0 where that is negative.  Identical inputs give exactly 0, an all-zero vector
+ *          contributes 0 as the package's 0 / (0 + eps) does, a NaN reaches its own image's results.  w[k] is the layer's
+ *          1x1 convolution, C[k] floats on the device.  out (device, n_images x (n_layers + 1) doubles): out[n][k] the
+ *          spatial mean of d, out[n][n_layers] their sum in layer order.  A work unit is up to ssg_featmetric_unit()
+ *          pixels of one image of one layer (fewer for a layer of fewer pixels: the power of two at or above H W, its
+ *          channels split over the rest of the workgroup); at most ssg_featmetric_grid_cap() workgroups, grid-stride
+ *          beyond.  Workspace: 8 bytes per unit.
+ *   ssg_dists_score    per (image, layer, channel) plane the sums of x, y, x^2, y^2, x y over chunks of
+ *          ssg_featmetric_chunk() elements of ONE plane (5 doubles per chunk in `workspace`, chunks ordered layer, image,
+ *          channel, chunk of the plane), then mx = Sx / HW, vx = Sxx / HW - mx^2, cov = Sxy / HW - mx my, S1 = (2 mx my +
+ *          c1) / (mx^2 + my^2 + c1), S2 = (2 cov + c2) / (vx + vy + c2), c1 = c2 = 1e-6; alpha, beta: sum_k C[k] floats on
+ *          the device, layer after layer.  out (device, n_images x 3 doubles): {1 - (s1 + s2) / ws, s1 / ws, s2 / ws}
+ *          with s1 = sum alpha_c S1, s2 = sum beta_c S2, ws = sum alpha + sum beta, channels in a fixed order.
+ * f0, f1, w, x, y are HOST arrays of n_layers device addresses (as size_t); C, H, W HOST arrays of n_layers ints.  The
+ * records travel in the kernels' arguments.  No allocation, copy, synchronisation or host read.
+ * ssg_*_workspace_bytes: 0 where the shapes would be refused.
+ * Status, decided before any launch with the outputs untouched: SSG_E_BADARG for a null pointer, array or address,
+ * n_layers outside 1 .. 16, n_images < 1, C, H or W < 1; SSG_E_TOOLARGE for H W or a unit / chunk count beyond INT_MAX;
+ * SSG_E_WORKSPACE for workspace_bytes below the reported size; SSG_E_ALIGN for a float address that is not 4-byte
+ * aligned or a workspace or out that is not 8-byte aligned. */
+int ssg_featmetric_grid_cap(void);
+int ssg_featmetric_unit(void);
+int ssg_featmetric_chunk(void);
+size_t ssg_lpips_workspace_bytes(int n_layers, int n_images, const int *C, const int *H, const int *W);
+int ssg_lpips_layers(int n_layers, int n_images, const size_t *f0, const size_t *f1, const size_t *w, const int *C,
+                     const int *H, const int *W, void *workspace, size_t workspace_bytes, double *out /* device */,
+                     ssg_stream_t stream);
+size_t ssg_dists_workspace_bytes(int n_layers, int n_images, const int *C, const int *H, const int *W);
+int ssg_dists_score(int n_layers, int n_images, const size_t *x, const size_t *y, const int *C, const int *H,
+                    const int *W, const float *alpha /* device */, const float *beta /* device */, void *workspace,
+                    size_t workspace_bytes, double *out /* device */, ssg_stream_t stream);
 
 #ifdef SSG_PROFILE
 /* PROFILING BUILD ONLY (libssg_hip_prof.so, compiled with -DSSG_PROFILE; the product library libssg_hip.so does not

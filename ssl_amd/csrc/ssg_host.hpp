@@ -160,6 +160,19 @@ int launch_mcrit_sums(size_t K, const size_t *x, const size_t *g, const size_t *
 int launch_mcrit_grad(size_t K, const size_t *x, const size_t *g, const size_t *grad, const size_t *counts,
                       const double *w, int kind, float eps, const double *sums, const double *coef, hipStream_t st);
 
+// ---- ssg_featmetric.hip: the LPIPS and DISTS criteria over a ragged set of feature pairs (entry points beside its
+// kernels, where the layer records are built) ----
+namespace featmetric {
+struct LpipsSet;
+struct DistsSet;
+}  // namespace featmetric
+int featmetric_grid_cap();
+int featmetric_unit();
+int featmetric_chunk();
+int launch_lpips_layers(const featmetric::LpipsSet &s, void *workspace, double *out, hipStream_t st);
+int launch_dists_score(const featmetric::DistsSet &s, const float *alpha, const float *beta, void *workspace, double *out,
+                       hipStream_t st);
+
 // ---- ssg_blindsr.hip: BSRGAN's degradation chain on a ragged batch, one launch per operation family (entry points
 // beside its kernels) ----
 int blindsr_grid_cap();

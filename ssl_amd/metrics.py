@@ -13,7 +13,12 @@ NIQE (section (K)): `calculate_niqe` keeps the reference's signature, `niqe` is 
 `MetricAverager.add_niqe` its running mean.  It is computed in fp64 from the rounded plane on.  The pristine model
 (mu_pris_param, cov_pris_param) is the reference's data and does not ship with the package: `load_niqe_params` takes
 it from a path, a mapping, the environment variable SSL_AMD_NIQE_PARAMS or an installed basicsr.  `calculate_metric`
-and `add_all` do not dispatch to NIQE (no reference YAML lists it under val.metrics)."""
+and `add_all` do not dispatch to NIQE (no reference YAML lists it under val.metrics).
+
+LPIPS and DISTS (section (V)), the other two entries of the reference's val.metrics blocks, live in
+ssl_amd/metrics_feat.py and are re-exported here: `calculate_lpips`, `calculate_dists`, the batched `lpips_dists`, the
+`LPIPS` and `DISTS` modules, `MetricAverager.add_lpips` / `add_dists`; `calculate_metric` and `add_all` dispatch on
+their types.  Unlike the metrics above they have a CPU path (the packages' torch lines)."""
 import importlib.util
 import os
 from copy import deepcopy
@@ -21,11 +26,12 @@ from copy import deepcopy
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, metrics_feat
 from .engine import _launch, _need_gpu, _ptr, _workspace
+from .metrics_feat import DISTS, LPIPS, calculate_dists, calculate_lpips, lpips_dists  # noqa: F401
 
 __all__ = ["calculate_psnr", "calculate_ssim", "calculate_niqe", "calculate_metric", "psnr_ssim", "niqe",
-           "load_niqe_params", "MetricAverager"]
+           "load_niqe_params", "MetricAverager", "calculate_lpips", "calculate_dists", "lpips_dists", "LPIPS", "DISTS"]
 
 KIND_F32_RGB, KIND_U8_HWC, KIND_U8_CHW = (_lib.CONSTANTS["SSG_METRIC_" + k] for k in ("F32_RGB", "U8_HWC", "U8_CHW"))
 KIND_F32_PLANE = _lib.CONSTANTS["SSG_NIQE_F32_PLANE"]   # NIQE only: a float32 (B,H,W) plane (input_order 'HW')
@@ -284,9 +290,20 @@ def calculate_metric(data, opt):
     """basicsr.metrics.calculate_metric: dispatches on opt['type'].  Floating-point TENSORS in `data` (img=, img2=) are
     taken for a model's (C,H,W) / (1,C,H,W) RGB tensors in [0, 1] and go through the quantising path, so a validation
     loop can drop tensor2img; arrays and uint8 tensors are images as the reference passes them."""
-    opt = deepcopy(opt)
-    col = _column(opt.pop('type'))
+    # (a state_dict given as lpips_weights= / dists_weights= is handed on as the object it is: the networks are cached per
+    # weights source, and a copy would be a new source, and a new network, per call)
+    weights = {k: opt[k] for k in metrics_feat.WEIGHT_OPTIONS if k in opt}
+    opt = dict(deepcopy({k: v for k, v in opt.items() if k not in weights}), **weights)
+    metric_type = opt.pop('type')
     img, img2 = data['img'], data['img2']
+    if metric_type in metrics_feat.FEATURE_METRICS:
+        if _is_model_tensor(img) and _is_model_tensor(img2):
+            out = metrics_feat.batched(metric_type, img, img2, opt)
+            if out.shape[0] != 1:
+                raise ValueError("ssl_amd: calculate_metric takes one image per call (lpips_dists is the batched call)")
+            return float(out[0])
+        return (calculate_lpips if metric_type == "calculate_lpips" else calculate_dists)(img, img2, **opt)
+    col = _column(metric_type)
     if _is_model_tensor(img) and _is_model_tensor(img2):
         opt.pop('input_order', None)
         out = psnr_ssim(img, img2, opt.get('crop_border', 0), opt.get('test_y_channel', False))
@@ -320,13 +337,19 @@ class MetricAverager:
         self._count[name] = self._count.get(name, 0) + values.numel()
 
     def add(self, name, sr, gt, **opt):
-        col = _column(opt.get('type', 'calculate_' + name))
+        metric_type = opt.get('type', 'calculate_' + name)
+        if metric_type in metrics_feat.FEATURE_METRICS:
+            return self._accumulate(name, metrics_feat.batched(metric_type, sr, gt, opt))
+        col = _column(metric_type)
         out = psnr_ssim(sr, gt, opt.get('crop_border', 0), opt.get('test_y_channel', False))
         self._accumulate(name, out[:, col])
 
     def add_all(self, sr, gt, metrics):
         done = {}
         for name, opt in metrics.items():
+            if opt.get('type', 'calculate_' + name) in metrics_feat.FEATURE_METRICS:
+                self.add(name, sr, gt, **opt)
+                continue
             col = _column(opt.get('type', 'calculate_' + name))
             key = (int(opt.get('crop_border', 0)), bool(opt.get('test_y_channel', False)))
             if key not in done:
@@ -338,6 +361,14 @@ class MetricAverager:
         niqe_pris_params."""
         out = niqe(sr, opt.get('crop_border', 0), opt.get('convert_to', 'y'), opt.get('niqe_pris_params'))
         self._accumulate(name, out)
+
+    def add_lpips(self, name, sr, gt, **opt):
+        """One LPIPS value per image (float RGB tensors in [0, 1]); opt: crop_border, lpips_weights, lpips_net."""
+        self._accumulate(name, metrics_feat.batched("calculate_lpips", sr, gt, opt))
+
+    def add_dists(self, name, sr, gt, **opt):
+        """One DISTS value per image (float RGB tensors in [0, 1]); opt: crop_border, dists_weights."""
+        self._accumulate(name, metrics_feat.batched("calculate_dists", sr, gt, opt))
 
     def result(self):
         if not self._sum:

@@ -12,7 +12,7 @@ FLAGS = "-O3 -std=c++17 -fPIC --offload-arch=gfx950 -munsafe-fp-atomics -Wno-unu
 EXTRA = {"ssg_dense": ["-fno-slp-vectorize"], "ssg_bwd_dense": ["-fno-slp-vectorize"]}   # the Makefile's EXTRA, file by file
 EXTRA.update({f: ["-ffp-contract=off"] for f in (
     "ssg_degrade", "ssg_ldl", "ssg_bbl", "ssg_metrics", "ssg_niqe", "ssg_colorfix", "ssg_ssim", "ssg_gan", "ssg_spsr",
-    "ssg_resample", "ssg_imresize", "ssg_multi", "ssg_mcrit", "ssg_blindsr")})
+    "ssg_resample", "ssg_imresize", "ssg_multi", "ssg_mcrit", "ssg_featmetric", "ssg_blindsr")})
 FILES = sys.argv[2:] or ["ssg_fwd", "ssg_dense", "ssg_bwd", "ssg_bwd_dense", "ssg_grow", "ssg_edges", "ssg_datapath", "ssg_degrade",
                          "ssg_ldl"]
 KEYS = ["VGPRs", "AGPRs", "TotalSGPRs", "ScratchSize [bytes/lane]", "VGPRs Spill", "LDS Size [bytes/block]", "Occupancy [waves/SIMD]"]
