@@ -35,7 +35,7 @@ import torch
 
 from . import _lib
 from .datapath import Draws, USMSharp, augment_crop, jpeg_roundtrip
-from .engine import _ptr, _stream
+from ._gpu import current_gpu, launch, on, ptr as _ptr
 
 __all__ = ["fspecial_gaussian", "fspecial", "anisotropic_Gaussian", "gm_blur_kernel", "shift_pixel", "add_blur",
            "add_resize", "add_Gaussian_noise", "add_speckle_noise", "add_Poisson_noise", "add_sharpening", "add_JPEG_noise",
@@ -388,14 +388,15 @@ def _upload(host, device):
     return torch.from_numpy(host).to(device)
 
 
-def _launch(family, table_ptr, n_tiles, in_ptr, out_ptr, field_ptr, pool_ptr):
+def _launch_family(dev, family, table_ptr, n_tiles, in_ptr, out_ptr, field_ptr, pool_ptr):
+    """the family's entry point over one table, on `dev` (each takes the arguments its kernels read)"""
     L = _lib.lib()
     if family == CONV:
-        _lib.check(L.ssg_blindsr_conv(table_ptr, n_tiles, in_ptr, out_ptr, pool_ptr, _stream()))
+        launch(dev, L.ssg_blindsr_conv, table_ptr, n_tiles, in_ptr, out_ptr, pool_ptr)
     elif family == RESIZE:
-        _lib.check(L.ssg_blindsr_resize(table_ptr, n_tiles, in_ptr, out_ptr, _stream()))
+        launch(dev, L.ssg_blindsr_resize, table_ptr, n_tiles, in_ptr, out_ptr)
     else:
-        _lib.check(L.ssg_blindsr_noise(table_ptr, n_tiles, in_ptr, out_ptr, field_ptr, pool_ptr, _stream()))
+        launch(dev, L.ssg_blindsr_noise, table_ptr, n_tiles, in_ptr, out_ptr, field_ptr, pool_ptr)
 
 
 def _noise_planes(op, C):
@@ -430,7 +431,7 @@ def ragged_apply(family, images, stages, fields=None):
         in_off, out_off, field_off = in_off + x.numel(), out_off + planes_o * st.oh * st.ow, field_off + planes_f * st.h * st.w
     pool_host = pool.array()
     table, n_tiles = fill_table(family, recs, in_off, out_off, field_off, pool_host.size)
-    with torch.cuda.device(dev):
+    with on(dev):
         src = torch.cat([x.reshape(-1) for x in images])
         dst = torch.empty(out_off, dtype=torch.float32, device=dev)
         fld = None
@@ -438,7 +439,7 @@ def ragged_apply(family, images, stages, fields=None):
             fld = torch.cat([f.to(device=dev, dtype=torch.float32).reshape(-1) for f, r in zip(fields, recs)
                              if _noise_planes(int(r["op"]), int(r["C"]))[0]])
         blob = _upload(np.concatenate([table, pool_host.view(np.uint8)]), dev)
-        _launch(family, blob.data_ptr(), n_tiles, _ptr(src), _ptr(dst), _ptr(fld), blob.data_ptr() + table.size)
+        _launch_family(dev, family, blob.data_ptr(), n_tiles, _ptr(src), _ptr(dst), _ptr(fld), blob.data_ptr() + table.size)
     return [dst[o:o + p * h * w].view(p, h, w) for o, p, h, w in outs]
 
 
@@ -464,9 +465,7 @@ def _device(images):
     for t in images:
         if torch.is_tensor(t) and t.is_cuda:
             return t.device
-    if not torch.cuda.is_available():
-        raise RuntimeError("ssl_amd.blindsr: the degradation chain runs on the GPU and none is visible; there is no CPU path")
-    return torch.device("cuda", torch.cuda.current_device())
+    return current_gpu("ssl_amd.blindsr: the degradation chain runs on the GPU and none is visible; there is no CPU path")
 
 
 def _align(n, a=4):
@@ -584,7 +583,7 @@ def run_stages(images, stage_lists, draws=None, trace=None):
             raise ValueError(f"ssl_amd.blindsr: image {i} is {tuple(x.shape[1:])} and its first stage takes ({h}, {w})")
     plan = _Plan(channels, stage_lists)
     host = plan.finish()
-    with torch.cuda.device(dev):
+    with on(dev):
         buf = torch.empty(max(2 * plan.arena, 1), dtype=torch.float32, device=dev)
         for i, x in enumerate(images):
             buf[plan.where(i, 0):plan.where(i, 0) + x.numel()].copy_(x.reshape(-1))
@@ -595,17 +594,17 @@ def run_stages(images, stage_lists, draws=None, trace=None):
             for key in ("conv", "resize"):
                 if step[key]:
                     fam, at, n_tiles = step[key]
-                    _launch(fam, base + at, n_tiles, _ptr(buf), _ptr(buf), None, pool_ptr)
+                    _launch_family(dev, fam, base + at, n_tiles, _ptr(buf), _ptr(buf), None, pool_ptr)
             if step["noise"]:
                 field = draws.randn((step["n_normal"],), dev) if step["n_normal"] else None
                 if step["rates"]:
                     rates = torch.empty(step["n_draws"], dtype=torch.float32, device=dev)
                     fam, at, n_tiles = step["rates"]
-                    _launch(fam, base + at, n_tiles, _ptr(buf), _ptr(rates), None, pool_ptr)
+                    _launch_family(dev, fam, base + at, n_tiles, _ptr(buf), _ptr(rates), None, pool_ptr)
                     drawn = draws.poisson(rates).to(torch.float32)
                     field = drawn if field is None else torch.cat([field.reshape(-1), drawn])
                 fam, at, n_tiles = step["noise"]
-                _launch(fam, base + at, n_tiles, _ptr(buf), _ptr(buf), _ptr(field.contiguous()), pool_ptr)
+                _launch_family(dev, fam, base + at, n_tiles, _ptr(buf), _ptr(buf), _ptr(field.contiguous()), pool_ptr)
             for (C, h, w), group in step["jpeg"].items():
                 n = C * h * w
                 batch = torch.stack([buf[s:s + n].view(C, h, w) for s, _, _ in group])

@@ -14,7 +14,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .engine import _launch, _need_gpu, _ptr, _workspace
+from ._gpu import launch as _launch, need_gpu as _need_gpu, ptr as _ptr, workspace as _workspace
 
 __all__ = ["wavelet_blur", "wavelet_decomposition", "wavelet_reconstruction", "calc_mean_std",
            "adaptive_instance_normalization", "adain_color_fix", "wavelet_color_fix", "color_fix"]

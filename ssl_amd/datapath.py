@@ -23,7 +23,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .engine import _need_gpu, _ptr, _stream
+from ._gpu import current_gpu, launch, need_gpu as _need_gpu, on, ptr as _ptr
 
 
 def draw_augment(hflip=True, rotation=True):
@@ -61,9 +61,7 @@ def augment_crop(x, out_hw, top_left, flips=None):
         rows.append([top, left, h, v, r])
     params = torch.tensor(rows, dtype=torch.int32).to(x.device, non_blocking=True)
     out = torch.empty((B, C, Ho, Wo), dtype=x.dtype, device=x.device)
-    with torch.cuda.device(x.device):
-        _lib.check(_lib.lib().ssg_augment_crop(_ptr(x), _ptr(out), x.element_size(), B, C, Hs, Ws, Ho, Wo, _ptr(params),
-                                               _stream()))
+    launch(x.device, _lib.lib().ssg_augment_crop, _ptr(x), _ptr(out), x.element_size(), B, C, Hs, Ws, Ho, Wo, _ptr(params))
     return out
 
 
@@ -112,10 +110,9 @@ class PairPool:
             self.slot = self.slot[idx]
             slots = self.slot[:b].to(torch.int32).to(lq.device, non_blocking=True)
             L = _lib.lib()
-            with torch.cuda.device(lq.device):
+            with on(lq.device):
                 for q, t in zip(self.q, batch):
-                    _lib.check(L.ssg_pool_swap(_ptr(q), _ptr(t), t[0].numel() * t.element_size(), _ptr(slots), b,
-                                               _stream()))
+                    launch(lq.device, L.ssg_pool_swap, _ptr(q), _ptr(t), t[0].numel() * t.element_size(), _ptr(slots), b)
             return tuple(batch)
         for q, t in zip(self.q, batch):
             q[self.queue_ptr:self.queue_ptr + b] = t
@@ -143,9 +140,8 @@ class USMSharp(torch.nn.Module):
         out = torch.empty_like(x)
         nb = L.ssg_usm_scratch_bytes(B, C, H, W)
         scratch = torch.empty(max(nb, 1), dtype=torch.uint8, device=x.device)
-        with torch.cuda.device(x.device):
-            _lib.check(L.ssg_usm_sharp(x.data_ptr(), out.data_ptr(), B, C, H, W, self.radius, self.sigma, float(weight),
-                                       float(threshold), scratch.data_ptr(), nb, torch.cuda.current_stream().cuda_stream))
+        launch(x.device, L.ssg_usm_sharp, x.data_ptr(), out.data_ptr(), B, C, H, W, self.radius, self.sigma, float(weight),
+               float(threshold), scratch.data_ptr(), nb)
         return out.to(img.dtype)
 
 
@@ -162,9 +158,7 @@ def filter2D(img, kernel):
     kk = kernel.detach().to(torch.float32).contiguous()
     B, C, H, W = x.shape
     out = torch.empty_like(x)
-    with torch.cuda.device(x.device):
-        _lib.check(_lib.lib().ssg_filter2d(x.data_ptr(), kk.data_ptr(), out.data_ptr(), B, C, H, W, k, kk.size(0),
-                                           torch.cuda.current_stream().cuda_stream))
+    launch(x.device, _lib.lib().ssg_filter2d, x.data_ptr(), kk.data_ptr(), out.data_ptr(), B, C, H, W, k, kk.size(0))
     return out.to(img.dtype)
 
 
@@ -194,9 +188,7 @@ class DiffJPEG(torch.nn.Module):
             qd, qh = quality.detach().to(device=xi.device, dtype=torch.float32).contiguous(), 0.0
             if qd.numel() != B:
                 raise ValueError("quality tensor needs one entry per sample")
-        with torch.cuda.device(xi.device):
-            _lib.check(_lib.lib().ssg_diffjpeg(xi.data_ptr(), out.data_ptr(), B, H, W, None if qd is None else qd.data_ptr(),
-                                               qh, torch.cuda.current_stream().cuda_stream))
+        launch(xi.device, _lib.lib().ssg_diffjpeg, xi.data_ptr(), out.data_ptr(), B, H, W, _ptr(qd), qh)
         return out.to(x.dtype)
 
 
@@ -219,9 +211,7 @@ def _jpeg_qualities(quality, B):
 
 def _jpeg_device():
     """where a numpy image goes: the current GPU"""
-    if not torch.cuda.is_available():
-        raise RuntimeError("ssl_amd.datapath: the JPEG round trip runs on the GPU and none is visible; there is no CPU path")
-    return torch.device("cuda", torch.cuda.current_device())
+    return current_gpu("ssl_amd.datapath: the JPEG round trip runs on the GPU and none is visible; there is no CPU path")
 
 
 def _jpeg_call(x, B, H, W, C, quality, in_f32, out_f32):
@@ -240,9 +230,8 @@ def _jpeg_call(x, B, H, W, C, quality, in_f32, out_f32):
     out_epilogue = K["SSG_JPEG_OUT_F32_NCHW" if out_f32 else "SSG_JPEG_OUT_U8_HWC"]
     nbytes = L.ssg_jpeg_roundtrip_workspace_bytes(B, H, W, C)
     ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=x.device)
-    with torch.cuda.device(x.device):
-        _lib.check(L.ssg_jpeg_roundtrip(_ptr(x), _ptr(out), B, H, W, C, qs.ctypes.data, in_layout, out_epilogue, _ptr(ws),
-                                        nbytes, _stream()))
+    launch(x.device, L.ssg_jpeg_roundtrip, _ptr(x), _ptr(out), B, H, W, C, qs.ctypes.data, in_layout, out_epilogue,
+           _ptr(ws), nbytes)
     return out
 
 
@@ -376,9 +365,8 @@ def interpolate(img, size=None, scale_factor=None, mode="bilinear"):
         raise RuntimeError(f"Input and output sizes should be greater than 0, but got input (H: {H}, W: {W}) "
                            f"output (H: {Ho}, W: {Wo})")
     out = torch.empty((B, C, Ho, Wo), dtype=torch.float32, device=x.device)
-    with torch.cuda.device(x.device):
-        _lib.check(_lib.lib().ssg_resize(_ptr(x), _ptr(out), B, C, H, W, Ho, Wo, _RESIZE_MODES[mode], float(sfh),
-                                         float(sfw), _stream()))
+    launch(x.device, _lib.lib().ssg_resize, _ptr(x), _ptr(out), B, C, H, W, Ho, Wo, _RESIZE_MODES[mode], float(sfh),
+           float(sfw))
     return out.to(img.dtype)
 
 
@@ -387,8 +375,7 @@ def clamp_round(img, clip=True, rounds=True):
     """`torch.clamp((out * 255.0).round(), 0, 255) / 255.` (realesrganssl_model.py:206,297) for clip = rounds = True."""
     x = _gpu_f32(img, "clamp_round")
     out = torch.empty_like(x)
-    with torch.cuda.device(x.device):
-        _lib.check(_lib.lib().ssg_clamp_round(_ptr(x), _ptr(out), x.numel(), int(clip), int(rounds), _stream()))
+    launch(x.device, _lib.lib().ssg_clamp_round, _ptr(x), _ptr(out), x.numel(), int(clip), int(rounds))
     return out.to(img.dtype)
 
 
@@ -454,9 +441,8 @@ def add_gaussian_noise(img, sigma, gray, field_color, field_gray=None, clip=True
     out = torch.empty_like(x)
     f32 = lambda t: None if t is None else t.detach().to(device=x.device, dtype=torch.float32).contiguous()
     sg, gr, fc, fg = f32(sigma), f32(gray), f32(field_color), f32(field_gray)
-    with torch.cuda.device(x.device):
-        _lib.check(_lib.lib().ssg_gaussian_noise(_ptr(x), _ptr(out), _ptr(fc), _ptr(fg), _ptr(sg), _ptr(gr), B, C, H, W,
-                                                 int(clip), int(rounds), _stream()))
+    launch(x.device, _lib.lib().ssg_gaussian_noise, _ptr(x), _ptr(out), _ptr(fc), _ptr(fg), _ptr(sg), _ptr(gr), B, C, H, W,
+           int(clip), int(rounds))
     return out.to(img.dtype)
 
 
@@ -471,8 +457,7 @@ def poisson_rates(img, with_gray):
     rg = torch.empty((B, 1, H, W), dtype=torch.float32, device=x.device) if with_gray else None
     vals = torch.empty((B, 2), dtype=torch.float32, device=x.device)
     scratch = torch.empty(L.ssg_poisson_scratch_bytes(B), dtype=torch.uint8, device=x.device)
-    with torch.cuda.device(x.device):
-        _lib.check(L.ssg_poisson_rates(_ptr(x), _ptr(rate), _ptr(rg), _ptr(vals), _ptr(scratch), B, C, H, W, _stream()))
+    launch(x.device, L.ssg_poisson_rates, _ptr(x), _ptr(rate), _ptr(rg), _ptr(vals), _ptr(scratch), B, C, H, W)
     return rate, rg, vals
 
 
@@ -485,9 +470,8 @@ def add_poisson_noise(img, scale, gray, vals, draw_color, draw_gray=None, clip=T
     out = torch.empty_like(x)
     f32 = lambda t: None if t is None else t.detach().to(device=x.device, dtype=torch.float32).contiguous()
     sc, gr, dc, dg, vv = f32(scale), f32(gray), f32(draw_color), f32(draw_gray), f32(vals)
-    with torch.cuda.device(x.device):
-        _lib.check(_lib.lib().ssg_poisson_noise(_ptr(x), _ptr(out), _ptr(dc), _ptr(dg), _ptr(vv), _ptr(sc), _ptr(gr), B, C,
-                                                H, W, int(clip), int(rounds), _stream()))
+    launch(x.device, _lib.lib().ssg_poisson_noise, _ptr(x), _ptr(out), _ptr(dc), _ptr(dg), _ptr(vv), _ptr(sc), _ptr(gr), B,
+           C, H, W, int(clip), int(rounds))
     return out.to(img.dtype)
 
 
@@ -546,8 +530,7 @@ def synth_kernels(records, pad_to, device=None):
     n = len(host)
     out = torch.empty((n, int(pad_to), int(pad_to)), dtype=torch.float32, device=device)
     staged = torch.empty(max(n, 1) * _RECORD_DTYPE.itemsize, dtype=torch.uint8, device=device)
-    with torch.cuda.device(device):
-        _lib.check(_lib.lib().ssg_synth_kernels(host.ctypes.data, n, int(pad_to), _ptr(staged), _ptr(out), _stream()))
+    launch(device, _lib.lib().ssg_synth_kernels, host.ctypes.data, n, int(pad_to), _ptr(staged), _ptr(out))
     return out
 
 

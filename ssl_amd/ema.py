@@ -26,7 +26,6 @@ strides and dtype of every tensor with the cached ones and rebuilds the table on
 Parameters only, not buffers, as in the reference.  The Parameter OBJECTS of ModelEma are those of its construction, and
 LitEma's trainable set is that of its construction.
 """
-import contextlib
 import operator
 import weakref
 
@@ -34,12 +33,10 @@ import torch
 from torch import nn
 from torch.nn.parallel import DataParallel, DistributedDataParallel
 
-from . import _lib
-from .engine import address_array
-from .engine import dense_strides as _dense
+from . import _gpu, _lib
+from ._gpu import address_array
+from ._gpu import dense_strides as _dense
 from .losses import basic_loss
-from .losses.gan_loss import _RAW_STREAM
-from .losses.gan_loss import _on as _on_cuda
 
 __all__ = ["ModelEma", "model_ema", "update_E", "LitEma", "get_bare_model"]
 
@@ -61,15 +58,10 @@ def _on_gpu(t):
     return t.is_cuda
 
 
-def _on(device):
-    """The context in which `device` is current."""
-    return _on_cuda(device) if device.type == "cuda" else contextlib.nullcontext()
-
-
 def _upload(host, device):
     """The table image on `device`, copied from the pinned `host` tensor on the current stream and waited for (at build
     time only: a later call may run on any stream)."""
-    with _on(device):
+    with _gpu.on(device):
         table = torch.empty(host.numel(), dtype=torch.uint8, device=device).copy_(host, non_blocking=True)
         torch.cuda.current_stream().synchronize()
     return table
@@ -77,12 +69,6 @@ def _upload(host, device):
 
 def _host_buffer(nbytes, device):
     return torch.empty(nbytes, dtype=torch.uint8, pin_memory=device.type == "cuda" and torch.cuda.is_available())
-
-
-def _stream(device):
-    if device.type != "cuda":
-        return None
-    return _RAW_STREAM(device.index) if _RAW_STREAM else torch.cuda.current_stream().cuda_stream
 
 
 def _native_pair(e, p):
@@ -187,9 +173,7 @@ class _Updater:
             d, a = (float(decay), 1 - float(decay)) if kind == EMA else (0.0, 0.0)
             for device, table, n_chunks, _ in self._tables:
                 wd = None if w is None else (w if w.device == device else w.to(device))
-                with _on(device):
-                    _lib.check(L.ssg_multi_apply(table.data_ptr(), n_chunks, kind, d, a,
-                                                 None if wd is None else wd.data_ptr(), _stream(device)))
+                _gpu.launch(device, L.ssg_multi_apply, table.data_ptr(), n_chunks, kind, d, a, _gpu.ptr(wd))
         if self._fallback:
             with torch.no_grad():
                 for e, p in self._fallback:

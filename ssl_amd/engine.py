@@ -10,36 +10,13 @@ sys.exit()).
 import torch
 
 from . import _lib
-
-
-def _ptr(t):
-    return None if t is None else t.data_ptr()
-
-
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
-
-
-def _need_gpu(*tensors):
-    for t in tensors:
-        if t is not None and not t.is_cuda:
-            raise RuntimeError(f"ssl_amd: expected a GPU tensor, got device {t.device}; the SSG engine has no CPU path")
+# the launch helpers under the names this module (and its tests and tools) has always used for them
+from ._gpu import address_array, dense_strides, launch as _launch, need_gpu as _need_gpu, ptr as _ptr  # noqa: F401
+from ._gpu import stream as _stream, workspace as _workspace  # noqa: F401
 
 
 def _f32c(t):
     return t.detach().to(torch.float32).contiguous()
-
-
-def _launch(dev, fn, *args):
-    """One call of the C ABI on the GPU that holds the call's tensors (whatever the current device is), on torch's
-    current stream of that GPU -- the last argument of every launching entry point."""
-    with torch.cuda.device(dev):
-        _lib.check(fn(*args, _stream()))
-
-
-def _workspace(nbytes, dev):
-    """(buffer, nbytes) for a size the library reported: at least one byte, so that the pointer is never NULL."""
-    return torch.empty(max(nbytes, 1), dtype=torch.uint8, device=dev), nbytes
 
 
 def _mask_kind(mask, image_channels):
@@ -440,12 +417,9 @@ class LossStep:
 
         def launch():
             # (ssg_loss_step: the gradient is an output of the call -- no fill kernel in front of it)
-            with torch.cuda.device(self.grad.device):
-                _lib.check(_lib.lib().ssg_loss_step(_ptr(sr), _ptr(gt), _ptr(mp), kind, mc, B, C, H, W, ks, kw,
-                                                       sigma, eps, gen, w_l1, w_kl, stride, thr, self.capacity,
-                                                       _ptr(self.ssg_sr), _ptr(self.ssg_gt), _ptr(self.counts),
-                                                       _ptr(self.loss), _ptr(self.grad), _ptr(self.ws), self.ws_bytes,
-                                                       _ptr(self.fix), _stream()))
+            _launch(self.grad.device, _lib.lib().ssg_loss_step, _ptr(sr), _ptr(gt), _ptr(mp), kind, mc, B, C, H, W, ks, kw,
+                    sigma, eps, gen, w_l1, w_kl, stride, thr, self.capacity, _ptr(self.ssg_sr), _ptr(self.ssg_gt),
+                    _ptr(self.counts), _ptr(self.loss), _ptr(self.grad), _ptr(self.ws), self.ws_bytes, _ptr(self.fix))
 
         if not self.use_graph:
             launch()
@@ -1030,25 +1004,6 @@ def pixel_loss(pred, target, kind='mse', eps=1e-12, loss_weight=1.0, reduction='
 
 # ------------------------------ a pixel criterion over a ragged set of tensor pairs (ssg_mcrit.hip, section (U)) ----
 MULTI_KINDS = dict(PIXEL_KINDS, fro=_lib.CONSTANTS["SSG_PIX_FRO"])
-
-
-def dense_strides(t):
-    """Non-overlapping and dense: the strides are those of some permutation of a contiguous layout (contiguous,
-    channels_last, any other permutation without gaps), so that one flat walk over the memory of two such tensors of
-    equal strides meets corresponding elements.  Dimensions of size 1 do not count, whatever their strides.  The one
-    spelling of this for the ragged kernels' callers (multi_pair_is_native here, ssl_amd/ema.py)."""
-    expect = 1
-    for stride, size in sorted((st, sz) for sz, st in zip(t.shape, t.stride()) if sz != 1):
-        if stride != expect:
-            return False
-        expect *= size
-    return True
-
-
-def address_array(values):
-    """Host addresses or element counts as the size_t array that the ragged entry points take (pass .ctypes.data)."""
-    import numpy as np
-    return np.ascontiguousarray(values, dtype=np.uintp)
 
 
 def multi_pair_is_native(pred, target):

@@ -18,7 +18,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from .. import engine
+from .. import _gpu, _lib, engine
 
 _reduction_modes = ['none', 'mean', 'sum']
 
@@ -55,14 +55,11 @@ class _CriterionSum(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, pred, target, which):
-        from .. import _lib
         L = _lib.lib()
         a, b = pred.contiguous(), target.detach().contiguous()
         sums = torch.empty(2, dtype=torch.float32, device=a.device)
         scratch = torch.empty(L.ssg_criteria_scratch_bytes(), dtype=torch.uint8, device=a.device)
-        with torch.cuda.device(a.device):
-            _lib.check(L.ssg_criteria_sums(a.data_ptr(), b.data_ptr(), a.numel(), scratch.data_ptr(), sums.data_ptr(),
-                                           torch.cuda.current_stream().cuda_stream))
+        _gpu.launch(a.device, L.ssg_criteria_sums, a.data_ptr(), b.data_ptr(), a.numel(), scratch.data_ptr(), sums.data_ptr())
         ctx.save_for_backward(a, b)
         ctx.which = which
         return sums[which]
@@ -70,14 +67,12 @@ class _CriterionSum(torch.autograd.Function):
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, g):
-        from .. import _lib
         a, b = ctx.saved_tensors
         coef = torch.zeros(2, dtype=torch.float32, device=a.device)
         coef[ctx.which] = g.to(torch.float32).reshape(())
         grad = torch.empty_like(a)
-        with torch.cuda.device(a.device):
-            _lib.check(_lib.lib().ssg_criteria_grad(a.data_ptr(), b.data_ptr(), a.numel(), coef.data_ptr(), grad.data_ptr(),
-                                                    torch.cuda.current_stream().cuda_stream))
+        _gpu.launch(a.device, _lib.lib().ssg_criteria_grad, a.data_ptr(), b.data_ptr(), a.numel(), coef.data_ptr(),
+                    grad.data_ptr())
         return grad, None, None
 
 

@@ -16,14 +16,12 @@ autograd replay.  Everything else -- CPU tensors, fp64, half / bf16, and, after 
 derivative through the criterion (the native node is once-differentiable) -- takes the torch expressions below, which
 are the reference's operations and give its bits.
 """
-import contextlib
-
 import torch
 import torch.nn.functional as F
 from torch import nn
 from torch.autograd.function import once_differentiable
 
-from .. import _lib
+from .. import _gpu, _lib
 from . import basic_loss
 
 __all__ = ["GANLoss", "MultiScaleGANLoss"]
@@ -44,9 +42,6 @@ def _native(*tensors):
 
 
 _CONSTANTS, _WORKSPACES = {}, {}
-# the current stream's handle without a Stream object around it (a call here is a handful of launches: the host's time
-# per call is what is left to save); torch.cuda.current_stream() where this torch has no such function
-_RAW_STREAM = getattr(torch._C, "_cuda_getCurrentRawStream", None)
 
 
 def _const(device, *values):
@@ -61,39 +56,31 @@ def _const(device, *values):
     return t
 
 
-def _launch(device):
-    """(library, stream handle, the sums' workspace) for a call on `device`, which is current.  One workspace per device
-    and stream: calls on one stream run in order, calls on different streams never share one."""
-    L = _lib.lib()
-    stream = _RAW_STREAM(device.index) if _RAW_STREAM else torch.cuda.current_stream().cuda_stream
+def _sums_workspace(device, stream):
+    """One workspace of the sums per device and stream: calls on one stream run in order, calls on different streams
+    never share one."""
     work = _WORKSPACES.get((device, stream))
     if work is None:
-        work = _WORKSPACES[(device, stream)] = torch.empty(L.ssg_gan_workspace_bytes(), dtype=torch.uint8, device=device)
-    return L, stream, work
-
-
-def _on(device):
-    """The context in which `device` is current (nothing to do where it already is)."""
-    return contextlib.nullcontext() if torch.cuda.current_device() == device.index else torch.cuda.device(device)
+        work = _WORKSPACES[(device, stream)] = torch.empty(_lib.lib().ssg_gan_workspace_bytes(), dtype=torch.uint8,
+                                                           device=device)
+    return work
 
 
 def _sums(x, spec, shift=None):
     """(sum l(d), sum l'(d)) of the contiguous fp32 GPU tensor x as two device doubles; shift: one device float."""
     out = torch.empty(2, dtype=torch.float64, device=x.device)
-    with _on(x.device):
-        L, stream, work = _launch(x.device)
-        _lib.check(L.ssg_gan_sums(x.data_ptr(), x.numel(), *spec, None if shift is None else shift.data_ptr(),
-                                  work.data_ptr(), out.data_ptr(), stream))
+    with _gpu.on(x.device):     # (not _gpu.launch: the stream's handle picks the workspace as well)
+        stream = _gpu.stream(x.device)
+        _lib.check(_lib.lib().ssg_gan_sums(x.data_ptr(), x.numel(), *spec, _gpu.ptr(shift),
+                                           _sums_workspace(x.device, stream).data_ptr(), out.data_ptr(), stream))
     return out
 
 
 def _grad(x, spec, shift, coef):
     """(float)(coef[0] l'(d) + coef[1]) in the shape of the contiguous x; coef: two device doubles."""
     grad = torch.empty_like(x)
-    with _on(x.device):
-        L, stream, _ = _launch(x.device)
-        _lib.check(L.ssg_gan_grad(x.data_ptr(), x.numel(), *spec, None if shift is None else shift.data_ptr(),
-                                  coef.data_ptr(), grad.data_ptr(), stream))
+    _gpu.launch(x.device, _lib.lib().ssg_gan_grad, x.data_ptr(), x.numel(), *spec, _gpu.ptr(shift), coef.data_ptr(),
+                grad.data_ptr())
     return grad
 
 

@@ -35,8 +35,9 @@ import torch
 import torch.nn.functional as F
 
 from .. import _lib, engine
+from .._gpu import launch, on, ptr as _ptr
 
-_ptr, _stream, _f32c = engine._ptr, engine._stream, engine._f32c
+_f32c = engine._f32c
 
 _LAZY = os.environ.get("SSG_LAZY", "1") not in ("", "0")
 # The eager-cliff warning (LazySSG._compute): rows computed image by image cost several times the batched step.  It is
@@ -306,7 +307,7 @@ class _LazyStepFn(torch.autograd.Function):
         x = _f32c(x_in)
         B, C, H, W = x.shape
         dev = x.device
-        with torch.cuda.device(dev):
+        with on(dev):
             dense = (ks, kw, C) in ((25, 9, 3), (49, 13, 3))      # sizes whose kernels all work from the plan
             el = engine.edge_list(mask=mask, capacity=B * H * W, ks=ks, order=not dense)
             n = int(el.counts[0])        # ONE host synchronisation per step (the loop itself has one per image)
@@ -324,13 +325,12 @@ class _LazyStepFn(torch.autograd.Function):
                 rsc = torch.empty(2 * n, dtype=torch.float64, device=dev)   # deferred normalisation (ssg_hip.h)
             else:
                 rank = plan = None
-            _lib.check(L.ssg_map_forward(_ptr(x), _ptr(y), B, C, H, W, _ptr(el.edges), _ptr(order), _ptr(rank),
-                                         _ptr(plan), _ptr(el.counts), n, ks, kw, sigma, eps, gen, _ptr(ssg_sr),
-                                         _ptr(ssg_gt), _ptr(rsc), _stream()))
+            launch(dev, L.ssg_map_forward, _ptr(x), _ptr(y), B, C, H, W, _ptr(el.edges), _ptr(order), _ptr(rank),
+                   _ptr(plan), _ptr(el.counts), n, ks, kw, sigma, eps, gen, _ptr(ssg_sr), _ptr(ssg_gt), _ptr(rsc))
             scratch = torch.empty(L.ssg_loss_scratch_bytes(B, H, W, n, ks), dtype=torch.uint8, device=dev)
-            _lib.check(L.ssg_loss_backward(_ptr(x), B, C, H, W, _ptr(el.edges), _ptr(order), _ptr(rank), _ptr(plan),
-                                           _ptr(el.counts), n, ks, kw, sigma, gen, _ptr(ssg_sr), _ptr(ssg_gt), 1.0,
-                                           1.0, None, _ptr(loss), None, _ptr(scratch), None, _ptr(rsc), 1, _stream()))
+            launch(dev, L.ssg_loss_backward, _ptr(x), B, C, H, W, _ptr(el.edges), _ptr(order), _ptr(rank), _ptr(plan),
+                   _ptr(el.counts), n, ks, kw, sigma, gen, _ptr(ssg_sr), _ptr(ssg_gt), 1.0, 1.0, None, _ptr(loss), None,
+                   _ptr(scratch), None, _ptr(rsc), 1)
         count = torch.full((), float(n * P), dtype=torch.float32, device=dev)
         ctx.mark_non_differentiable(count)
         ctx.save_for_backward(x, el.edges, el.counts, ssg_sr, ssg_gt)
@@ -349,16 +349,15 @@ class _LazyStepFn(torch.autograd.Function):
         ks, kw, sigma, gen, det = ctx.cfg
         B, C, H, W = x.shape
         dev, n = x.device, ctx.n
-        with torch.cuda.device(dev):
+        with on(dev):
             up = torch.stack([g_l1.to(torch.float32).reshape(()), g_kl.to(torch.float32).reshape(())]).contiguous()
             grad = torch.zeros_like(x)
             loss = torch.empty(2, dtype=torch.float32, device=dev)
             scratch = torch.empty(L.ssg_loss_scratch_bytes(B, H, W, n, ks), dtype=torch.uint8, device=dev)
             fix = engine._grad_fix(det, x)
-            _lib.check(L.ssg_loss_backward(_ptr(x), B, C, H, W, _ptr(edges), _ptr(order), _ptr(rank), _ptr(plan),
-                                           _ptr(counts), n, ks, kw, sigma, gen, _ptr(ssg_sr), _ptr(ssg_gt), 1.0, 1.0,
-                                           _ptr(up), _ptr(loss), _ptr(grad), _ptr(scratch), _ptr(fix), _ptr(rsc), 1,
-                                           _stream()))
+            launch(dev, L.ssg_loss_backward, _ptr(x), B, C, H, W, _ptr(edges), _ptr(order), _ptr(rank), _ptr(plan),
+                   _ptr(counts), n, ks, kw, sigma, gen, _ptr(ssg_sr), _ptr(ssg_gt), 1.0, 1.0, _ptr(up), _ptr(loss),
+                   _ptr(grad), _ptr(scratch), _ptr(fix), _ptr(rsc), 1)
         return (grad.to(ctx.in_dtype),) + (None,) * 8
 
 

@@ -6,13 +6,13 @@ psize), differentiable w.r.t. `image`), backed by ssg_compute_similarity /
 ssg_compute_similarity_backward of include/ssg_hip.h instead of the JIT-built
 CUDA extension.  Differences by design: tensors that are not on the GPU raise
 RuntimeError (the reference logs and calls sys.exit(), :60-62); nothing is
-compiled at import; kernels run on torch's current stream and the two
-torch.cuda.synchronize() calls of the reference backward (:50,53) are gone.
+compiled at import; kernels run on the image's GPU and torch's current stream
+there, and the two torch.cuda.synchronize() calls of the reference backward (:50,53) are gone.
 """
 import torch
 import torch.nn.functional as F
 
-from ... import _lib
+from ... import _gpu, _lib
 
 
 class _DistanceOp(torch.autograd.Function):
@@ -21,9 +21,8 @@ class _DistanceOp(torch.autograd.Function):
         channel, height, width = image_pad.shape
         mc = pos.shape[0]
         out = torch.zeros((mc, psize, psize), dtype=torch.float32, device=image_pad.device)
-        _lib.check(_lib.lib().ssg_compute_similarity(
-            image_pad.data_ptr(), pos.data_ptr(), out.data_ptr(), mc, psize, ksize, height, width, channel,
-            torch.cuda.current_stream().cuda_stream))
+        _gpu.launch(image_pad.device, _lib.lib().ssg_compute_similarity, image_pad.data_ptr(), pos.data_ptr(),
+                    out.data_ptr(), mc, psize, ksize, height, width, channel)
         ctx.save_for_backward(image_pad, pos)
         ctx.sizes = (psize, ksize)
         return out
@@ -36,9 +35,8 @@ class _DistanceOp(torch.autograd.Function):
         channel, height, width = image_pad.shape
         grads = grad_output.to(torch.float32).contiguous()
         image_grad = torch.zeros_like(image_pad)
-        _lib.check(_lib.lib().ssg_compute_similarity_backward(
-            image_pad.data_ptr(), grads.data_ptr(), pos.data_ptr(), image_grad.data_ptr(), pos.shape[0], psize, ksize,
-            height, width, channel, torch.cuda.current_stream().cuda_stream))
+        _gpu.launch(image_pad.device, _lib.lib().ssg_compute_similarity_backward, image_pad.data_ptr(), grads.data_ptr(),
+                    pos.data_ptr(), image_grad.data_ptr(), pos.shape[0], psize, ksize, height, width, channel)
         return image_grad, None, None, None
 
 

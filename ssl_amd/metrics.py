@@ -27,7 +27,7 @@ import numpy as np
 import torch
 
 from . import _lib, metrics_feat
-from .engine import _launch, _need_gpu, _ptr, _workspace
+from ._gpu import current_gpu, launch as _launch, need_gpu as _need_gpu, ptr as _ptr, workspace as _workspace
 from .metrics_feat import DISTS, LPIPS, calculate_dists, calculate_lpips, lpips_dists  # noqa: F401
 
 __all__ = ["calculate_psnr", "calculate_ssim", "calculate_niqe", "calculate_metric", "psnr_ssim", "niqe",
@@ -42,7 +42,7 @@ _CONVERT = {'y': 0, 'gray': 1}
 
 
 def _device():
-    return torch.device("cuda", torch.cuda.current_device())
+    return current_gpu("ssl_amd.metrics: the metrics run on the GPU and none is visible; there is no CPU path")
 
 
 def _run(a, b, kind, B, C, H, W, crop_border, y_channel):

@@ -28,7 +28,7 @@ import torch.nn.functional as F
 from torch import nn
 
 from . import _lib
-from .engine import _launch, _ptr, _workspace, address_array
+from ._gpu import address_array, launch as _launch, ptr as _ptr, workspace as _workspace
 from .losses import basic_loss
 from .losses.perceptual import build_vgg_trunk, vgg_layer_names
 

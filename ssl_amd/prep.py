@@ -20,7 +20,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .engine import _launch, _need_gpu, _ptr
+from ._gpu import current_gpu, launch as _launch, need_gpu as _need_gpu, ptr as _ptr
 
 __all__ = ["resize", "load_img", "from_pil", "multiscale", "multiscale_plan", "subimage_grid", "extract_subimages",
            "subimage_name", "FILTERS", "imresize", "imresize_np", "modcrop"]
@@ -113,9 +113,7 @@ def resize(img, size, resample='lanczos', out='uint8'):
 
 
 def _current_device():
-    if not torch.cuda.is_available():
-        raise RuntimeError("ssl_amd: the resize runs on the GPU and none is visible; there is no CPU path")
-    return torch.device("cuda", torch.cuda.current_device())
+    return current_gpu("ssl_amd: the resize runs on the GPU and none is visible; there is no CPU path")
 
 
 def from_pil(image, device=None):

@@ -168,8 +168,8 @@ def main():
         blob = torch.from_numpy(np.concatenate([table, ph.view(np.uint8)])).to(dev)
         src, dst = torch.cat([x.reshape(-1) for x in planar]), torch.empty(n_out, device=dev)
         fld = torch.cat([f.reshape(-1) for f in fields]) if fields else None
-        call = lambda: blindsr._launch(fam, blob.data_ptr(), n_tiles, src.data_ptr(), dst.data_ptr(),
-                                       None if fld is None else fld.data_ptr(), blob.data_ptr() + table.size)
+        call = lambda: blindsr._launch_family(dev, fam, blob.data_ptr(), n_tiles, src.data_ptr(), dst.data_ptr(),
+                                              None if fld is None else fld.data_ptr(), blob.data_ptr() + table.size)
         ms = event_ms(call, 20, args.rounds, 3)
         floor = 4 * (n_in + n_out + (n_in if fields else 0)) / HBM_BYTES_PER_S * 1e3
         lines.append(f"  {name:22s} {ms * 1e3:8.1f} us   floor {floor * 1e3:6.1f} us   {100 * floor / ms:5.1f} % of the floor's rate")
