@@ -80,6 +80,9 @@ typedef void *ssg_stream_t; /* hipStream_t */
  * SSG_PIX_FRO (a pixel criterion over a ragged set of tensor pairs: the perceptual loss, section (U)). */
 /* 6, additive: + ssg_lpips_layers, ssg_dists_score, ssg_lpips_workspace_bytes, ssg_dists_workspace_bytes,
  * ssg_featmetric_grid_cap / _unit / _chunk (the LPIPS and DISTS criteria over their feature pairs, section (V)). */
+/* 6, additive: + ssg_diff_combine, ssg_diff_p_sample, ssg_diff_loss_sums, ssg_diff_loss_finish, ssg_diff_loss_grad,
+ * ssg_diff_canvas_gather, ssg_diff_canvas_stitch, ssg_diff_workspace_bytes, ssg_diff_chunk, ssg_diff_grid_cap and
+ * SSG_DIFF_EPS / _X0 / _V (the Diffusion fork around its network, section (W)). */
 int ssg_abi_version(void);
 const char *ssg_status_string(int status);
 /* Device-side refusals that no return value can carry (everything is asynchronous): waits for `stream`, then returns
@@ -1218,6 +1221,84 @@ size_t ssg_dists_workspace_bytes(int n_layers, int n_images, const int *C, const
 int ssg_dists_score(int n_layers, int n_images, const size_t *x, const size_t *y, const int *C, const int *H,
                     const int *W, const float *alpha /* device */, const float *beta /* device */, void *workspace,
                     size_t workspace_bytes, double *out /* device */, ssg_stream_t stream);
+
+/* ---------------------------------------------------------------- (W) ----
+ * What surrounds the Diffusion fork's U-Net (Diffusion-Based-SR/ldm/models/diffusion/ddpm.py and ddpmssl.py), outside
+ * the network, ssl_amd/csrc/ssg_diffusion.hip: the per-sample linear combinations of the schedule, p_sample behind the
+ * network call, the training criterion of p_losses, and the tile gather / weighted stitch of p_mean_variance_canvas.
+ * Tensors are (B, n) fp32 contiguous, B >= 1, n >= 1; a sample's base needs only a float's alignment.  t is B int64 ON
+ * THE DEVICE, every table T fp32 on the device; tab[t_b] is gathered by the kernels and NO entry point reads t on the
+ * host.  A t_b outside [0, T) reads nothing: that sample's coefficients, and so its results, are NaN.  Every fp32
+ * operation is rounded on its own, in the reference's order (no fma): on the same tables the elementwise results are
+ * torch's bits.  A chunk is ssg_diff_chunk() elements of ONE sample; at most ssg_diff_grid_cap() workgroups of 256
+ * threads, further chunks grid-stride.  One writer per output element, no atomics, no scratch, no allocation, copy,
+ * synchronisation or host read; results are the same bits from call to call, and sample b of a batch gives the bits
+ * of that sample alone (for ssg_diff_loss_finish: its S_b).
+ *   ssg_diff_combine   out = fl(fl(A[t_b] x) + fl(Bt[t_b] y)) (subtract != 0: -), then, clamp != 0, the clamp to [lo, hi]
+ *          (a NaN stays).  q_sample, get_v, predict_start_from_noise, predict_start_from_z_and_v, q_posterior's mean.
+ *   ssg_diff_p_sample  x_recon = fl(fl(ra[t_b] x) - fl(rb[t_b] model_out)) for SSG_DIFF_EPS (ra, rb = sqrt_recip_ /
+ *          sqrt_recipm1_alphas_cumprod) and SSG_DIFF_V (sqrt_alphas_cumprod / sqrt_one_minus_alphas_cumprod), model_out
+ *          for SSG_DIFF_X0 (ra, rb unused, may be NULL); clip != 0: clamped to [-1, 1]; mean = fl(fl(c1[t_b] x_recon) +
+ *          fl(c2[t_b] x)); out = fl(mean + fl(fl(m_b sigma[t_b]) noise)), m_b = (t_b != 0); x_recon to x0_out (nullable).
+ *   ssg_diff_loss_sums   one fp64 partial per chunk of sum_i l(target - pred) in `workspace` (8 bytes per chunk,
+ *          ssg_diff_workspace_bytes(B, n)); kind SSG_PIX_L1 (|d|) or SSG_PIX_MSE (d d): l in fp32, widened, added in fp64
+ *          in an order that depends on n alone, not on the sample's alignment.
+ *   ssg_diff_loss_finish   ONE workgroup, fp64: S_b = the sample's partials in chunk order (sums_out, B doubles); mean_b
+ *          = S_b / n; wbar = mean_b(p2[t_b]) (p2 NULL: 1), the weight of EVERY sample -- the reference multiplies its (B,)
+ *          loss_simple by a (B, 1, 1, 1) weight, and the mean of the (B, 1, 1, B) result is this (ddpmssl.py:397-401);
+ *          (with p2 one t_b outside the table therefore makes every sample's results NaN);
+ *          l_b = wbar mean_b / exp(logvar[t_b]) + logvar[t_b];
+ *          scalars_out (4 doubles) = {loss_simple = mean_b(mean_b), loss_gamma = mean_b(l_b), loss_vlb =
+ *          mean_b(lvlb[t_b] mean_b), loss = l_simple_weight loss_gamma + original_elbo_weight loss_vlb}, the reference's
+ *          loss_dict; coef_out[b] = dloss / dmean_b = (l_simple_weight wbar / exp(logvar[t_b]) + original_elbo_weight
+ *          lvlb[t_b]) / B; dlogvar_out (nullable, T doubles) = dloss / dlogvar, the samples of equal t added IN SAMPLE
+ *          ORDER, 0 for a tau no sample has.  All outputs device memory.
+ *   ssg_diff_loss_grad   grad_pred[b, i] = (float)(g[0] coef[b] / n (double)(-l'(d))) - fl(rb[t_b] grad_x0[b, i]);
+ *          g (ONE FLOAT, the upstream gradient of the loss) and coef are read on the device.  grad_x0 (nullable): the
+ *          gradient that arrives through x0 = predict_start_from_noise(x_noisy, t, pred), rb = sqrt_recipm1_alphas_
+ *          cumprod; without it rb, t and T are unused.  l' of section (R): L1's is 0 at +-0.
+ *   ssg_diff_canvas_gather   out[(k B + b), c, y, x] = src[b, c, oy_k + y, ox_k + x]: ntiles B tiles of (C, ts, ts).
+ *   ssg_diff_canvas_stitch   out (B, C, h, w): per element, over the tiles that cover it IN TABLE ORDER, acc =
+ *          (float)((double)acc + (double)p w), cnt = (float)((double)cnt + w), out = acc / cnt in fp32 (NaN where no tile
+ *          covers): torch's in-place add of an fp64 product into an fp32 tensor.  p is element (c, y - oy_k, x - ox_k) of
+ *          tile preds[src_k + b bstep] (bstep 0: one tile for every sample, 1: a tile per sample), preds holding n_preds
+ *          tiles; w is weights[b wsb + c wsc + (y - oy_k) ts + (x - ox_k)], fp64 on the device, the caller's strides in
+ *          elements (0, 0: one plane), or 1 with weights NULL (an unweighted average).
+ * tiles: ntiles records {oy, ox, src} of three ints ON THE DEVICE.  A record whose square leaves the canvas or whose
+ * src + b bstep leaves [0, n_preds) is skipped by the kernels: nothing outside the tensors is read or written.
+ * Status, decided before any launch with the outputs untouched: SSG_E_BADARG for a null pointer (those marked nullable
+ * excepted), B, n, T, C, h, w, ts or ntiles < 1, ts > h or w, an unknown kind or param, a lo, hi, l_simple_weight or
+ * original_elbo_weight that is a NaN, lo > hi, bstep outside {0, 1}; SSG_E_TOOLARGE for a chunk count beyond INT_MAX, B
+ * beyond INT_MAX (ssg_diff_loss_finish) or a canvas or tile tensor of 2^31 elements or more; SSG_E_WORKSPACE for
+ * workspace_bytes < ssg_diff_workspace_bytes(B, n) (which is 0 where B and n would be refused); SSG_E_ALIGN for a float
+ * address that is not 4-byte aligned or a t, workspace, weights or double address that is not 8-byte aligned. */
+#define SSG_DIFF_EPS 0
+#define SSG_DIFF_X0 1
+#define SSG_DIFF_V 2
+int ssg_diff_chunk(void);
+int ssg_diff_grid_cap(void);
+size_t ssg_diff_workspace_bytes(size_t B, size_t n);
+int ssg_diff_combine(const float *x, const float *y, const long long *t, const float *A, const float *Bt, int T,
+                     size_t B, size_t n, int subtract, int clamp, float lo, float hi, float *out, ssg_stream_t stream);
+int ssg_diff_p_sample(const float *x, const float *model_out, const float *noise, const long long *t, const float *ra,
+                      const float *rb, const float *c1, const float *c2, const float *sigma, int T, size_t B, size_t n,
+                      int param, int clip, float *out, float *x0_out /* nullable */, ssg_stream_t stream);
+int ssg_diff_loss_sums(const float *pred, const float *target, size_t B, size_t n, int kind, void *workspace,
+                       size_t workspace_bytes, ssg_stream_t stream);
+int ssg_diff_loss_finish(const void *workspace, size_t workspace_bytes, const long long *t,
+                         const float *p2 /* nullable */, const float *logvar, const float *lvlb, int T, size_t B,
+                         size_t n, double l_simple_weight, double original_elbo_weight, double *sums_out,
+                         double *scalars_out, double *coef_out, double *dlogvar_out /* nullable */,
+                         ssg_stream_t stream);
+int ssg_diff_loss_grad(const float *pred, const float *target, const float *grad_x0 /* nullable */,
+                       const long long *t, const float *rb, int T, const float *g /* device */,
+                       const double *coef /* device */, size_t B, size_t n, int kind, float *grad_pred,
+                       ssg_stream_t stream);
+int ssg_diff_canvas_gather(const float *src, const int *tiles /* device */, int ntiles, int B, int C, int h, int w,
+                           int ts, float *out, ssg_stream_t stream);
+int ssg_diff_canvas_stitch(const float *preds, int n_preds, int bstep, const int *tiles /* device */, int ntiles,
+                           const double *weights /* nullable */, size_t wsb, size_t wsc, int B, int C, int h, int w,
+                           int ts, float *out, ssg_stream_t stream);
 
 #ifdef SSG_PROFILE
 /* PROFILING BUILD ONLY (libssg_hip_prof.so, compiled with -DSSG_PROFILE; the product library libssg_hip.so does not

@@ -4,6 +4,7 @@
 #include "../../include/ssg_hip.h"
 
 #include <atomic>
+#include <climits>
 #include <cstdlib>
 #include <mutex>
 
@@ -1597,6 +1598,113 @@ int ssg_pixel_grad(const float *pred, const float *target, size_t n, int kind, f
   if (unaligned(pred, 4) || unaligned(target, 4) || unaligned(grad_pred, 4) || unaligned(coef, 8))
     return SSG_E_ALIGN;
   return launch_pixel_grad(pred, target, n, kind, eps, coef, grad_pred, (hipStream_t)stream);
+}
+
+// ---- (W) the Diffusion fork around its network ----
+
+int ssg_diff_chunk(void) { return diff_chunk(); }
+
+int ssg_diff_grid_cap(void) { return diff_grid_cap(); }
+
+size_t ssg_diff_workspace_bytes(size_t B, size_t n) {
+  size_t cps = 0, total = 0;
+  return diff_chunks(B, n, &cps, &total) ? sizeof(double) * total : 0;
+}
+
+// what every per-sample entry point checks of its shape: (B, n) with a chunk count that fits, a table of T entries
+static int diff_check_shape(size_t B, size_t n, int T) {
+  size_t cps = 0, total = 0;
+  if (B < 1 || n < 1 || T < 1) return SSG_E_BADARG;
+  return diff_chunks(B, n, &cps, &total) ? 0 : SSG_E_TOOLARGE;
+}
+
+int ssg_diff_combine(const float *x, const float *y, const long long *t, const float *A, const float *Bt, int T,
+                     size_t B, size_t n, int subtract, int clamp, float lo, float hi, float *out, ssg_stream_t stream) {
+  if (!x || !y || !t || !A || !Bt || !out) return SSG_E_BADARG;
+  if (clamp && !(lo <= hi)) return SSG_E_BADARG;   // (a NaN fails the comparison)
+  if (const int rc = diff_check_shape(B, n, T)) return rc;
+  if (unaligned(x, 4) || unaligned(y, 4) || unaligned(A, 4) || unaligned(Bt, 4) || unaligned(out, 4) || unaligned(t, 8))
+    return SSG_E_ALIGN;
+  return launch_diff_combine(x, y, t, A, Bt, T, B, n, subtract, clamp, lo, hi, out, (hipStream_t)stream);
+}
+
+int ssg_diff_p_sample(const float *x, const float *model_out, const float *noise, const long long *t, const float *ra,
+                      const float *rb, const float *c1, const float *c2, const float *sigma, int T, size_t B, size_t n,
+                      int param, int clip, float *out, float *x0_out, ssg_stream_t stream) {
+  if (!x || !model_out || !noise || !t || !c1 || !c2 || !sigma || !out) return SSG_E_BADARG;
+  if (param < SSG_DIFF_EPS || param > SSG_DIFF_V || (param != SSG_DIFF_X0 && (!ra || !rb))) return SSG_E_BADARG;
+  if (const int rc = diff_check_shape(B, n, T)) return rc;
+  if (unaligned(x, 4) || unaligned(model_out, 4) || unaligned(noise, 4) || unaligned(ra, 4) || unaligned(rb, 4) ||
+      unaligned(c1, 4) || unaligned(c2, 4) || unaligned(sigma, 4) || unaligned(out, 4) || unaligned(x0_out, 4) ||
+      unaligned(t, 8))
+    return SSG_E_ALIGN;
+  return launch_diff_p_sample(x, model_out, noise, t, ra, rb, c1, c2, sigma, T, B, n, param, clip, out, x0_out,
+                              (hipStream_t)stream);
+}
+
+int ssg_diff_loss_sums(const float *pred, const float *target, size_t B, size_t n, int kind, void *workspace,
+                       size_t workspace_bytes, ssg_stream_t stream) {
+  if (!pred || !target || !workspace || (kind != SSG_PIX_L1 && kind != SSG_PIX_MSE)) return SSG_E_BADARG;
+  if (const int rc = diff_check_shape(B, n, 1)) return rc;
+  if (workspace_bytes < ssg_diff_workspace_bytes(B, n)) return SSG_E_WORKSPACE;
+  if (unaligned(pred, 4) || unaligned(target, 4) || unaligned(workspace, 8)) return SSG_E_ALIGN;
+  return launch_diff_loss_sums(pred, target, B, n, kind, workspace, (hipStream_t)stream);
+}
+
+int ssg_diff_loss_finish(const void *workspace, size_t workspace_bytes, const long long *t, const float *p2,
+                         const float *logvar, const float *lvlb, int T, size_t B, size_t n, double l_simple_weight,
+                         double original_elbo_weight, double *sums_out, double *scalars_out, double *coef_out,
+                         double *dlogvar_out, ssg_stream_t stream) {
+  if (!workspace || !t || !logvar || !lvlb || !sums_out || !scalars_out || !coef_out) return SSG_E_BADARG;
+  if (l_simple_weight != l_simple_weight || original_elbo_weight != original_elbo_weight) return SSG_E_BADARG;
+  if (const int rc = diff_check_shape(B, n, T)) return rc;
+  if (B > (size_t)INT_MAX) return SSG_E_TOOLARGE;
+  if (workspace_bytes < ssg_diff_workspace_bytes(B, n)) return SSG_E_WORKSPACE;
+  if (unaligned(workspace, 8) || unaligned(t, 8) || unaligned(p2, 4) || unaligned(logvar, 4) || unaligned(lvlb, 4) ||
+      unaligned(sums_out, 8) || unaligned(scalars_out, 8) || unaligned(coef_out, 8) || unaligned(dlogvar_out, 8))
+    return SSG_E_ALIGN;
+  return launch_diff_loss_finish(workspace, t, p2, logvar, lvlb, T, B, n, l_simple_weight, original_elbo_weight,
+                                 sums_out, scalars_out, coef_out, dlogvar_out, (hipStream_t)stream);
+}
+
+int ssg_diff_loss_grad(const float *pred, const float *target, const float *grad_x0, const long long *t,
+                       const float *rb, int T, const float *g, const double *coef, size_t B, size_t n, int kind,
+                       float *grad_pred, ssg_stream_t stream) {
+  if (!pred || !target || !g || !coef || !grad_pred || (kind != SSG_PIX_L1 && kind != SSG_PIX_MSE)) return SSG_E_BADARG;
+  if (grad_x0 && (!t || !rb)) return SSG_E_BADARG;
+  if (const int rc = diff_check_shape(B, n, grad_x0 ? T : 1)) return rc;
+  if (unaligned(pred, 4) || unaligned(target, 4) || unaligned(grad_x0, 4) || unaligned(rb, 4) || unaligned(g, 4) ||
+      unaligned(grad_pred, 4) || unaligned(t, 8) || unaligned(coef, 8))
+    return SSG_E_ALIGN;
+  return launch_diff_loss_grad(pred, target, grad_x0, t, rb, T, g, coef, B, n, kind, grad_pred, (hipStream_t)stream);
+}
+
+// the canvas (B, C, h, w), its tiles of (C, ts, ts) and the n_tiles of them in a tile tensor: each below 2^31 elements
+static int diff_check_canvas(int ntiles, int B, int C, int h, int w, int ts, long long n_tiles) {
+  if (ntiles < 1 || B < 1 || C < 1 || h < 1 || w < 1 || ts < 1 || ts > h || ts > w || n_tiles < 1) return SSG_E_BADARG;
+  const unsigned long long lim = 1ull << 31;
+  if ((unsigned long long)B * C >= lim || (unsigned long long)B * C * h >= lim || (unsigned long long)B * C * h * w >= lim)
+    return SSG_E_TOOLARGE;
+  if ((unsigned long long)C * ts * ts >= lim || (unsigned long long)n_tiles * C * ts * ts >= lim) return SSG_E_TOOLARGE;
+  return 0;
+}
+
+int ssg_diff_canvas_gather(const float *src, const int *tiles, int ntiles, int B, int C, int h, int w, int ts,
+                           float *out, ssg_stream_t stream) {
+  if (!src || !tiles || !out) return SSG_E_BADARG;
+  if (const int rc = diff_check_canvas(ntiles, B, C, h, w, ts, (long long)ntiles * B)) return rc;
+  if (unaligned(src, 4) || unaligned(tiles, 4) || unaligned(out, 4)) return SSG_E_ALIGN;
+  return launch_diff_canvas_gather(src, tiles, ntiles, B, C, h, w, ts, out, (hipStream_t)stream);
+}
+
+int ssg_diff_canvas_stitch(const float *preds, int n_preds, int bstep, const int *tiles, int ntiles,
+                           const double *weights, size_t wsb, size_t wsc, int B, int C, int h, int w, int ts,
+                           float *out, ssg_stream_t stream) {
+  if (!preds || !tiles || !out || (bstep != 0 && bstep != 1)) return SSG_E_BADARG;
+  if (const int rc = diff_check_canvas(ntiles, B, C, h, w, ts, n_preds)) return rc;
+  if (unaligned(preds, 4) || unaligned(tiles, 4) || unaligned(out, 4) || unaligned(weights, 8)) return SSG_E_ALIGN;
+  return launch_diff_canvas_stitch(preds, n_preds, bstep, tiles, ntiles, weights, wsb, wsc, B, C, h, w, ts, out,
+                                   (hipStream_t)stream);
 }
 
 int ssg_device_status(ssg_stream_t stream) {

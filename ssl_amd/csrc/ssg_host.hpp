@@ -160,6 +160,29 @@ int launch_mcrit_sums(size_t K, const size_t *x, const size_t *g, const size_t *
 int launch_mcrit_grad(size_t K, const size_t *x, const size_t *g, const size_t *grad, const size_t *counts,
                       const double *w, int kind, float eps, const double *sums, const double *coef, hipStream_t st);
 
+// ---- ssg_diffusion.hip: the Diffusion fork's schedule combinations, p_sample, training criterion and canvas stitch ----
+int diff_chunk();
+int diff_grid_cap();
+bool diff_chunks(size_t B, size_t n, size_t *per_sample, size_t *total);
+int launch_diff_combine(const float *x, const float *y, const long long *t, const float *A, const float *Bt, int T,
+                        size_t B, size_t n, int subtract, int clamp, float lo, float hi, float *out, hipStream_t st);
+int launch_diff_p_sample(const float *x, const float *model_out, const float *noise, const long long *t,
+                         const float *ra, const float *rb, const float *c1, const float *c2, const float *sigma, int T,
+                         size_t B, size_t n, int param, int clip, float *out, float *x0_out, hipStream_t st);
+int launch_diff_loss_sums(const float *pred, const float *target, size_t B, size_t n, int kind, void *workspace,
+                          hipStream_t st);
+int launch_diff_loss_finish(const void *workspace, const long long *t, const float *p2, const float *logvar,
+                            const float *lvlb, int T, size_t B, size_t n, double lsw, double elbo, double *sums_out,
+                            double *scalars_out, double *coef_out, double *dlogvar_out, hipStream_t st);
+int launch_diff_loss_grad(const float *pred, const float *target, const float *grad_x0, const long long *t,
+                          const float *rb, int T, const float *g, const double *coef, size_t B, size_t n, int kind,
+                          float *grad_pred, hipStream_t st);
+int launch_diff_canvas_gather(const float *src, const int *tiles, int ntiles, int B, int C, int h, int w, int ts,
+                              float *out, hipStream_t st);
+int launch_diff_canvas_stitch(const float *preds, int n_preds, int bstep, const int *tiles, int ntiles,
+                              const double *weights, size_t wsb, size_t wsc, int B, int C, int h, int w, int ts,
+                              float *out, hipStream_t st);
+
 // ---- ssg_featmetric.hip: the LPIPS and DISTS criteria over a ragged set of feature pairs (entry points beside its
 // kernels, where the layer records are built) ----
 namespace featmetric {
