@@ -1,6 +1,6 @@
-// C ABI of the gfx950 SSG engine: argument checking, workspace carving and
-// kernel dispatch.  See include/ssg_hip.h for the contract of every entry point
-// and the reference interface it replaces.
+// C ABI of the gfx950 SSG engine -- the edge list, the maps, the losses, the fused step, the operator and the process-wide
+// settings: argument checking, workspace carving and kernel dispatch.  See include/ssg_hip.h for the contract of every
+// entry point and the reference interface it replaces.  Every other family's entry points are defined beside its kernels.
 #include "../../include/ssg_hip.h"
 
 #include <atomic>
@@ -1382,65 +1382,6 @@ int ssg_loss_step(const float *sr, const float *gt, const void *mask, int mask_k
                            workspace, workspace_bytes, grad_fix, GradientIs::output, stream);
 }
 
-int ssg_augment_crop(const void *src, void *dst, int elem_bytes, int B, int C, int Hs, int Ws, int Ho, int Wo,
-                     const int *params, ssg_stream_t stream) {
-  if (!src || !dst || !params || B < 0 || C <= 0 || Hs <= 0 || Ws <= 0 || Ho <= 0 || Wo <= 0 ||
-      (elem_bytes != 1 && elem_bytes != 4))
-    return SSG_E_BADARG;
-  return launch_augment_crop(src, dst, elem_bytes, B, C, Hs, Ws, Ho, Wo, params, (hipStream_t)stream);
-}
-
-int ssg_pool_swap(void *queue, void *batch, size_t sample_bytes, const int *slots, int b, ssg_stream_t stream) {
-  if (!queue || !batch || !slots || b < 0) return SSG_E_BADARG;
-  return launch_pool_swap(queue, batch, sample_bytes, slots, b, (hipStream_t)stream);
-}
-
-size_t ssg_usm_scratch_bytes(int B, int C, int H, int W) { return usm_scratch_bytes(B, C, H, W); }
-
-int ssg_usm_sharp(const float *img, float *out, int B, int C, int H, int W, int radius, float sigma, float weight,
-                  float threshold, void *scratch, size_t scratch_bytes, ssg_stream_t stream) {
-  if (B < 0 || C <= 0 || H <= 0 || W <= 0 || radius < 0) return SSG_E_BADARG;
-  if (B == 0) return 0;
-  if (!img || !out || !scratch || img == out) return SSG_E_BADARG;
-  if (scratch_bytes < usm_scratch_bytes(B, C, H, W)) return SSG_E_WORKSPACE;
-  const int ksize = radius % 2 == 0 ? radius + 1 : radius;   // img_process_util.py:67-68
-  const int rc = launch_usm_sharp(img, out, B, C, H, W, ksize, sigma, weight, threshold, scratch, (hipStream_t)stream);
-  return rc == -1 ? SSG_E_BADARG : rc == -4 ? SSG_E_IMAGESMALL : rc;
-}
-
-int ssg_filter2d(const float *img, const float *kernels, float *out, int B, int C, int H, int W, int k, int n_kernels,
-                 ssg_stream_t stream) {
-  if (B < 0 || C <= 0 || H <= 0 || W <= 0) return SSG_E_BADARG;
-  if (B == 0) return 0;
-  if (!img || !kernels || !out || img == out) return SSG_E_BADARG;
-  const int rc = launch_filter2d(img, kernels, out, B, C, H, W, k, n_kernels, (hipStream_t)stream);
-  return rc == -1 ? SSG_E_BADARG : rc == -4 ? SSG_E_IMAGESMALL : rc;
-}
-
-int ssg_synth_kernels(const ssg_kernel_record *records, int n, int pad_to, ssg_kernel_record *records_dev, float *out,
-                      ssg_stream_t stream) {
-  if (n < 0 || pad_to < 1 || pad_to > SYNTH_MAX_PAD || !(pad_to & 1)) return SSG_E_BADARG;
-  if (n == 0) return 0;
-  if (!records || !records_dev || !out) return SSG_E_BADARG;
-  for (int i = 0; i < n; ++i) {
-    const ssg_kernel_record &r = records[i];
-    if (r.kind < SSG_KERNEL_PULSE || r.kind > SSG_KERNEL_PLATEAU) return SSG_E_BADARG;
-    if (r.size < 1 || !(r.size & 1) || r.size > pad_to) return SSG_E_BADARG;
-  }
-  const int rc = (int)hipMemcpyAsync(records_dev, records, (size_t)n * sizeof(ssg_kernel_record), hipMemcpyHostToDevice,
-                                     (hipStream_t)stream);
-  if (rc) return rc;
-  return launch_synth_kernels(records_dev, n, pad_to, out, (hipStream_t)stream);
-}
-
-int ssg_diffjpeg(const float *img, float *out, int B, int H, int W, const float *quality_dev, float quality,
-                 ssg_stream_t stream) {
-  if (B < 0 || H <= 0 || W <= 0) return SSG_E_BADARG;
-  if (B == 0) return 0;
-  if (!img || !out || (!quality_dev && !(quality > 0.f))) return SSG_E_BADARG;
-  return launch_jpeg(img, out, B, H, W, quality_dev, quality, (hipStream_t)stream);
-}
-
 int ssg_operator_pool_trim(void) {
   hipMemPool_t pool = op_pool();
   return pool ? (int)hipMemPoolTrimTo(pool, 0) : 0;
@@ -1450,261 +1391,6 @@ int ssg_set_operator_plan_threshold(int positions) {
   const int prev = op_plan_from();
   g_op_plan_from.store(positions > 0 ? positions : 0x7fffffff, std::memory_order_relaxed);
   return prev;
-}
-
-size_t ssg_criteria_scratch_bytes(void) { return criteria_scratch_bytes(); }
-
-int ssg_criteria_sums(const float *pred, const float *target, size_t n, void *scratch, float *sums_out,
-                      ssg_stream_t stream) {
-  if (!sums_out || !scratch) return SSG_E_BADARG;
-  if (n == 0) return (int)hipMemsetAsync(sums_out, 0, 2 * sizeof(float), (hipStream_t)stream);
-  if (!pred || !target) return SSG_E_BADARG;
-  return launch_criteria_sums(pred, target, n, scratch, sums_out, (hipStream_t)stream);
-}
-
-int ssg_criteria_grad(const float *pred, const float *target, size_t n, const float *coef, float *grad_pred,
-                      ssg_stream_t stream) {
-  if (n == 0) return 0;
-  if (!pred || !target || !coef || !grad_pred) return SSG_E_BADARG;
-  return launch_criteria_grad(pred, target, n, coef, grad_pred, (hipStream_t)stream);
-}
-
-size_t ssg_ssim_workspace_bytes(int B, int C, int H, int W) { return ssim_workspace_bytes(B, C, H, W); }
-
-int ssg_ssim_grid_cap(void) { return ssim_grid_cap(); }
-
-int ssg_ssim_taps(int window_size, float *taps_out) { return ssim_taps(window_size, taps_out); }
-
-int ssg_ssim_loss(const float *x, const float *y, int B, int C, int H, int W, int window_size, float *grad_x,
-                  double *sums_out, void *workspace, size_t workspace_bytes, ssg_stream_t stream) {
-  return launch_ssim_loss(x, y, B, C, H, W, window_size, grad_x, sums_out, workspace, workspace_bytes,
-                          (hipStream_t)stream);
-}
-
-size_t ssg_gan_workspace_bytes(void) { return gan_workspace_bytes(); }
-
-int ssg_gan_grid_cap(void) { return gan_grid_cap(); }
-
-// ---- the GAN criteria, SPSR's gradient map and the pixel criteria: every refusal is decided here, before any launch ----
-static bool unaligned(const void *p, size_t a) { return p && (size_t)p % a; }
-
-static int gan_check(const float *x, size_t n, int kind, float sign) {
-  if (!x || n == 0 || kind < SSG_GAN_BCE || kind > SSG_GAN_HINGE || !(sign == 1.f || sign == -1.f)) return SSG_E_BADARG;
-  return unaligned(x, 4) ? SSG_E_ALIGN : 0;   // (the head / float4 split assumes a float's own alignment)
-}
-
-int ssg_gan_sums(const float *x, size_t n, int kind, float sign, float label, const float *shift, void *workspace,
-                 double *sums_out, ssg_stream_t stream) {
-  if (const int rc = gan_check(x, n, kind, sign)) return rc;
-  if (!workspace || !sums_out) return SSG_E_BADARG;
-  if (unaligned(workspace, 8) || unaligned(sums_out, 8)) return SSG_E_ALIGN;
-  return launch_gan_sums(x, n, kind, sign, label, shift, workspace, sums_out, (hipStream_t)stream);
-}
-
-int ssg_gan_grad(const float *x, size_t n, int kind, float sign, float label, const float *shift, const double *coef,
-                 float *grad, ssg_stream_t stream) {
-  if (const int rc = gan_check(x, n, kind, sign)) return rc;
-  if (!coef || !grad) return SSG_E_BADARG;
-  if (unaligned(coef, 8) || unaligned(grad, 4)) return SSG_E_ALIGN;
-  return launch_gan_grad(x, n, kind, sign, label, shift, coef, grad, (hipStream_t)stream);
-}
-
-// ---- (R) SPSR's gradient map and the pixel criteria ----
-
-static int spsr_check_planes(int planes, int H, int W) {
-  if (planes < 1 || H < 1 || W < 1) return SSG_E_BADARG;
-  return (unsigned long long)planes * (unsigned long long)H * (unsigned long long)W >= (1ull << 31) ? SSG_E_BADARG : 0;
-}
-
-static int spsr_check_kind(int kind, float eps) {
-  if (kind < SSG_PIX_L1 || kind > SSG_PIX_CHARBONNIER) return SSG_E_BADARG;
-  return eps >= 0.f && eps <= 3.402823466e38f ? 0 : SSG_E_BADARG;   // (a NaN fails both comparisons)
-}
-
-size_t ssg_spsr_workspace_bytes(void) { return spsr_workspace_bytes(); }
-
-int ssg_spsr_grid_cap(void) { return spsr_grid_cap(); }
-
-int ssg_spsr_map(const float *x, int planes, int H, int W, float *map, ssg_stream_t stream) {
-  if (!x || !map) return SSG_E_BADARG;
-  if (const int rc = spsr_check_planes(planes, H, W)) return rc;
-  if (unaligned(x, 4) || unaligned(map, 4)) return SSG_E_ALIGN;
-  return launch_spsr_map(x, planes, H, W, map, (hipStream_t)stream);
-}
-
-int ssg_spsr_map_backward(const float *x, const float *grad_map, int planes, int H, int W, float *grad_x,
-                          ssg_stream_t stream) {
-  if (!x || !grad_map || !grad_x) return SSG_E_BADARG;
-  if (const int rc = spsr_check_planes(planes, H, W)) return rc;
-  if (unaligned(x, 4) || unaligned(grad_map, 4) || unaligned(grad_x, 4)) return SSG_E_ALIGN;
-  return launch_spsr_gather(x, nullptr, grad_map, nullptr, planes, H, W, SSG_PIX_L1, 0.f, grad_x, (hipStream_t)stream);
-}
-
-int ssg_spsr_loss(const float *x, const float *target, int planes, int H, int W, int kind, float eps, float *map_out,
-                  void *workspace, double *sum_out, ssg_stream_t stream) {
-  if (!x || !target || !workspace || !sum_out) return SSG_E_BADARG;
-  if (const int rc = spsr_check_planes(planes, H, W)) return rc;
-  if (const int rc = spsr_check_kind(kind, eps)) return rc;
-  if (unaligned(x, 4) || unaligned(target, 4) || unaligned(map_out, 4) || unaligned(workspace, 8) ||
-      unaligned(sum_out, 8))
-    return SSG_E_ALIGN;
-  return launch_spsr_loss(x, target, planes, H, W, kind, eps, map_out, workspace, sum_out, (hipStream_t)stream);
-}
-
-int ssg_spsr_loss_backward(const float *x, const float *target, const float *grad_map, const double *coef, int planes,
-                           int H, int W, int kind, float eps, float *grad_x, ssg_stream_t stream) {
-  if (!x || !target || !coef || !grad_x) return SSG_E_BADARG;
-  if (const int rc = spsr_check_planes(planes, H, W)) return rc;
-  if (const int rc = spsr_check_kind(kind, eps)) return rc;
-  if (unaligned(x, 4) || unaligned(target, 4) || unaligned(grad_map, 4) || unaligned(grad_x, 4) ||
-      unaligned(coef, 8))
-    return SSG_E_ALIGN;
-  return launch_spsr_gather(x, target, grad_map, coef, planes, H, W, kind, eps, grad_x, (hipStream_t)stream);
-}
-
-int ssg_spsr_branch_loss(const float *branch, const float *gt, int planes, int H, int W, int kind, float eps,
-                         void *workspace, double *sum_out, ssg_stream_t stream) {
-  if (!branch || !gt || !workspace || !sum_out) return SSG_E_BADARG;
-  if (const int rc = spsr_check_planes(planes, H, W)) return rc;
-  if (const int rc = spsr_check_kind(kind, eps)) return rc;
-  if (unaligned(branch, 4) || unaligned(gt, 4) || unaligned(workspace, 8) || unaligned(sum_out, 8))
-    return SSG_E_ALIGN;
-  return launch_spsr_branch_sums(branch, gt, planes, H, W, kind, eps, workspace, sum_out, (hipStream_t)stream);
-}
-
-int ssg_spsr_branch_grad(const float *branch, const float *gt, int planes, int H, int W, int kind, float eps,
-                         const double *coef, float *grad_branch, ssg_stream_t stream) {
-  if (!branch || !gt || !coef || !grad_branch) return SSG_E_BADARG;
-  if (const int rc = spsr_check_planes(planes, H, W)) return rc;
-  if (const int rc = spsr_check_kind(kind, eps)) return rc;
-  if (unaligned(branch, 4) || unaligned(gt, 4) || unaligned(grad_branch, 4) || unaligned(coef, 8))
-    return SSG_E_ALIGN;
-  return launch_spsr_branch_grad(branch, gt, planes, H, W, kind, eps, coef, grad_branch, (hipStream_t)stream);
-}
-
-int ssg_pixel_sums(const float *pred, const float *target, size_t n, int kind, float eps, void *workspace,
-                   double *sum_out, ssg_stream_t stream) {
-  if (!pred || !target || !workspace || !sum_out || n < 1) return SSG_E_BADARG;
-  if (const int rc = spsr_check_kind(kind, eps)) return rc;
-  if (unaligned(pred, 4) || unaligned(target, 4) || unaligned(workspace, 8) || unaligned(sum_out, 8))
-    return SSG_E_ALIGN;
-  return launch_pixel_sums(pred, target, n, kind, eps, workspace, sum_out, (hipStream_t)stream);
-}
-
-int ssg_pixel_grad(const float *pred, const float *target, size_t n, int kind, float eps, const double *coef,
-                   float *grad_pred, ssg_stream_t stream) {
-  if (!pred || !target || !coef || !grad_pred || n < 1) return SSG_E_BADARG;
-  if (const int rc = spsr_check_kind(kind, eps)) return rc;
-  if (unaligned(pred, 4) || unaligned(target, 4) || unaligned(grad_pred, 4) || unaligned(coef, 8))
-    return SSG_E_ALIGN;
-  return launch_pixel_grad(pred, target, n, kind, eps, coef, grad_pred, (hipStream_t)stream);
-}
-
-// ---- (W) the Diffusion fork around its network ----
-
-int ssg_diff_chunk(void) { return diff_chunk(); }
-
-int ssg_diff_grid_cap(void) { return diff_grid_cap(); }
-
-size_t ssg_diff_workspace_bytes(size_t B, size_t n) {
-  size_t cps = 0, total = 0;
-  return diff_chunks(B, n, &cps, &total) ? sizeof(double) * total : 0;
-}
-
-// what every per-sample entry point checks of its shape: (B, n) with a chunk count that fits, a table of T entries
-static int diff_check_shape(size_t B, size_t n, int T) {
-  size_t cps = 0, total = 0;
-  if (B < 1 || n < 1 || T < 1) return SSG_E_BADARG;
-  return diff_chunks(B, n, &cps, &total) ? 0 : SSG_E_TOOLARGE;
-}
-
-int ssg_diff_combine(const float *x, const float *y, const long long *t, const float *A, const float *Bt, int T,
-                     size_t B, size_t n, int subtract, int clamp, float lo, float hi, float *out, ssg_stream_t stream) {
-  if (!x || !y || !t || !A || !Bt || !out) return SSG_E_BADARG;
-  if (clamp && !(lo <= hi)) return SSG_E_BADARG;   // (a NaN fails the comparison)
-  if (const int rc = diff_check_shape(B, n, T)) return rc;
-  if (unaligned(x, 4) || unaligned(y, 4) || unaligned(A, 4) || unaligned(Bt, 4) || unaligned(out, 4) || unaligned(t, 8))
-    return SSG_E_ALIGN;
-  return launch_diff_combine(x, y, t, A, Bt, T, B, n, subtract, clamp, lo, hi, out, (hipStream_t)stream);
-}
-
-int ssg_diff_p_sample(const float *x, const float *model_out, const float *noise, const long long *t, const float *ra,
-                      const float *rb, const float *c1, const float *c2, const float *sigma, int T, size_t B, size_t n,
-                      int param, int clip, float *out, float *x0_out, ssg_stream_t stream) {
-  if (!x || !model_out || !noise || !t || !c1 || !c2 || !sigma || !out) return SSG_E_BADARG;
-  if (param < SSG_DIFF_EPS || param > SSG_DIFF_V || (param != SSG_DIFF_X0 && (!ra || !rb))) return SSG_E_BADARG;
-  if (const int rc = diff_check_shape(B, n, T)) return rc;
-  if (unaligned(x, 4) || unaligned(model_out, 4) || unaligned(noise, 4) || unaligned(ra, 4) || unaligned(rb, 4) ||
-      unaligned(c1, 4) || unaligned(c2, 4) || unaligned(sigma, 4) || unaligned(out, 4) || unaligned(x0_out, 4) ||
-      unaligned(t, 8))
-    return SSG_E_ALIGN;
-  return launch_diff_p_sample(x, model_out, noise, t, ra, rb, c1, c2, sigma, T, B, n, param, clip, out, x0_out,
-                              (hipStream_t)stream);
-}
-
-int ssg_diff_loss_sums(const float *pred, const float *target, size_t B, size_t n, int kind, void *workspace,
-                       size_t workspace_bytes, ssg_stream_t stream) {
-  if (!pred || !target || !workspace || (kind != SSG_PIX_L1 && kind != SSG_PIX_MSE)) return SSG_E_BADARG;
-  if (const int rc = diff_check_shape(B, n, 1)) return rc;
-  if (workspace_bytes < ssg_diff_workspace_bytes(B, n)) return SSG_E_WORKSPACE;
-  if (unaligned(pred, 4) || unaligned(target, 4) || unaligned(workspace, 8)) return SSG_E_ALIGN;
-  return launch_diff_loss_sums(pred, target, B, n, kind, workspace, (hipStream_t)stream);
-}
-
-int ssg_diff_loss_finish(const void *workspace, size_t workspace_bytes, const long long *t, const float *p2,
-                         const float *logvar, const float *lvlb, int T, size_t B, size_t n, double l_simple_weight,
-                         double original_elbo_weight, double *sums_out, double *scalars_out, double *coef_out,
-                         double *dlogvar_out, ssg_stream_t stream) {
-  if (!workspace || !t || !logvar || !lvlb || !sums_out || !scalars_out || !coef_out) return SSG_E_BADARG;
-  if (l_simple_weight != l_simple_weight || original_elbo_weight != original_elbo_weight) return SSG_E_BADARG;
-  if (const int rc = diff_check_shape(B, n, T)) return rc;
-  if (B > (size_t)INT_MAX) return SSG_E_TOOLARGE;
-  if (workspace_bytes < ssg_diff_workspace_bytes(B, n)) return SSG_E_WORKSPACE;
-  if (unaligned(workspace, 8) || unaligned(t, 8) || unaligned(p2, 4) || unaligned(logvar, 4) || unaligned(lvlb, 4) ||
-      unaligned(sums_out, 8) || unaligned(scalars_out, 8) || unaligned(coef_out, 8) || unaligned(dlogvar_out, 8))
-    return SSG_E_ALIGN;
-  return launch_diff_loss_finish(workspace, t, p2, logvar, lvlb, T, B, n, l_simple_weight, original_elbo_weight,
-                                 sums_out, scalars_out, coef_out, dlogvar_out, (hipStream_t)stream);
-}
-
-int ssg_diff_loss_grad(const float *pred, const float *target, const float *grad_x0, const long long *t,
-                       const float *rb, int T, const float *g, const double *coef, size_t B, size_t n, int kind,
-                       float *grad_pred, ssg_stream_t stream) {
-  if (!pred || !target || !g || !coef || !grad_pred || (kind != SSG_PIX_L1 && kind != SSG_PIX_MSE)) return SSG_E_BADARG;
-  if (grad_x0 && (!t || !rb)) return SSG_E_BADARG;
-  if (const int rc = diff_check_shape(B, n, grad_x0 ? T : 1)) return rc;
-  if (unaligned(pred, 4) || unaligned(target, 4) || unaligned(grad_x0, 4) || unaligned(rb, 4) || unaligned(g, 4) ||
-      unaligned(grad_pred, 4) || unaligned(t, 8) || unaligned(coef, 8))
-    return SSG_E_ALIGN;
-  return launch_diff_loss_grad(pred, target, grad_x0, t, rb, T, g, coef, B, n, kind, grad_pred, (hipStream_t)stream);
-}
-
-// the canvas (B, C, h, w), its tiles of (C, ts, ts) and the n_tiles of them in a tile tensor: each below 2^31 elements
-static int diff_check_canvas(int ntiles, int B, int C, int h, int w, int ts, long long n_tiles) {
-  if (ntiles < 1 || B < 1 || C < 1 || h < 1 || w < 1 || ts < 1 || ts > h || ts > w || n_tiles < 1) return SSG_E_BADARG;
-  const unsigned long long lim = 1ull << 31;
-  if ((unsigned long long)B * C >= lim || (unsigned long long)B * C * h >= lim || (unsigned long long)B * C * h * w >= lim)
-    return SSG_E_TOOLARGE;
-  if ((unsigned long long)C * ts * ts >= lim || (unsigned long long)n_tiles * C * ts * ts >= lim) return SSG_E_TOOLARGE;
-  return 0;
-}
-
-int ssg_diff_canvas_gather(const float *src, const int *tiles, int ntiles, int B, int C, int h, int w, int ts,
-                           float *out, ssg_stream_t stream) {
-  if (!src || !tiles || !out) return SSG_E_BADARG;
-  if (const int rc = diff_check_canvas(ntiles, B, C, h, w, ts, (long long)ntiles * B)) return rc;
-  if (unaligned(src, 4) || unaligned(tiles, 4) || unaligned(out, 4)) return SSG_E_ALIGN;
-  return launch_diff_canvas_gather(src, tiles, ntiles, B, C, h, w, ts, out, (hipStream_t)stream);
-}
-
-int ssg_diff_canvas_stitch(const float *preds, int n_preds, int bstep, const int *tiles, int ntiles,
-                           const double *weights, size_t wsb, size_t wsc, int B, int C, int h, int w, int ts,
-                           float *out, ssg_stream_t stream) {
-  if (!preds || !tiles || !out || (bstep != 0 && bstep != 1)) return SSG_E_BADARG;
-  if (const int rc = diff_check_canvas(ntiles, B, C, h, w, ts, n_preds)) return rc;
-  if (unaligned(preds, 4) || unaligned(tiles, 4) || unaligned(out, 4) || unaligned(weights, 8)) return SSG_E_ALIGN;
-  return launch_diff_canvas_stitch(preds, n_preds, bstep, tiles, ntiles, weights, wsb, wsc, B, C, h, w, ts, out,
-                                   (hipStream_t)stream);
 }
 
 int ssg_device_status(ssg_stream_t stream) {

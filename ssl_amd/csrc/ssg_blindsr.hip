@@ -403,10 +403,10 @@ static int check_record(int family, const ssg_blindsr_record &r, size_t in_elems
 
 }  // namespace blindsr
 
-int blindsr_grid_cap() { return blindsr::GRID_CAP; }
+static int blindsr_grid_cap() { return blindsr::GRID_CAP; }
 
-int launch_blindsr(int family, const void *table, int n_tiles, const float *in, float *out, const float *field,
-                   const float *pool, hipStream_t st) {
+static int launch_blindsr(int family, const void *table, int n_tiles, const float *in, float *out, const float *field,
+                          const float *pool, hipStream_t st) {
   using namespace blindsr;
   const dim3 grid((unsigned)std::min(n_tiles, GRID_CAP)), block(NT);
   const int *tab = (const int *)table;
@@ -442,7 +442,7 @@ int ssg_blindsr_table_fill(int family, const ssg_blindsr_record *records, int n_
   using namespace blindsr;
   if (family < SSG_BSR_CONV || family > SSG_BSR_NOISE || n_images < 0 || !table || !n_tiles_out) return SSG_E_BADARG;
   if (n_images && !records) return SSG_E_BADARG;
-  if ((size_t)table % sizeof(int)) return SSG_E_ALIGN;
+  if (unaligned(table, sizeof(int))) return SSG_E_ALIGN;
   if (in_elems > (size_t)UINT_MAX || out_elems > (size_t)UINT_MAX || field_elems > (size_t)UINT_MAX ||
       pool_elems > (size_t)UINT_MAX)
     return SSG_E_TOOLARGE;
@@ -488,8 +488,8 @@ int ssg_blindsr_table_fill(int family, const ssg_blindsr_record *records, int n_
 static int blindsr_apply(int family, const void *table, int n_tiles, const float *in, float *out, const float *field,
                          const float *pool, ssg_stream_t stream) {
   if (!table || !in || !out || n_tiles < 0) return SSG_E_BADARG;
-  if ((size_t)table % sizeof(int) || (size_t)in % sizeof(float) || (size_t)out % sizeof(float) ||
-      (size_t)field % sizeof(float) || (size_t)pool % sizeof(float))
+  if (unaligned(table, sizeof(int)) || unaligned(in, sizeof(float)) || unaligned(out, sizeof(float)) ||
+      unaligned(field, sizeof(float)) || unaligned(pool, sizeof(float)))
     return SSG_E_ALIGN;
   if (n_tiles == 0) return 0;
   return launch_blindsr(family, table, n_tiles, in, out, field, pool, (hipStream_t)stream);

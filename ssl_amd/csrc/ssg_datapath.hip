@@ -16,6 +16,9 @@
 //                      reference convolves with the 51 x 51 outer product; here the two blurs are separable row /
 //                      column passes through LDS tiles (2 x 51 instead of 2601 taps per pixel), the elementwise steps
 //                      ride in the column passes' epilogues: four launches, ~12 floats of HBM traffic per element.
+//   ssg_filter2d, ssg_diffjpeg : described in front of their kernels below.
+// This file defines the entry points ssg_augment_crop, ssg_pool_swap, ssg_usm_scratch_bytes, ssg_usm_sharp, ssg_filter2d
+// and ssg_diffjpeg, at its end.
 #include "ssg_host.hpp"
 
 namespace ssg {
@@ -56,35 +59,6 @@ __global__ __launch_bounds__(256) void pool_swap(V *queue, V *batch, size_t samp
     *q = c;
     batch[i] = a;
   }
-}
-
-int launch_augment_crop(const void *src, void *dst, int elem_bytes, int B, int C, int Hs, int Ws, int Ho, int Wo,
-                        const int *params, hipStream_t st) {
-  const size_t n = (size_t)B * C * Ho * Wo;
-  if (n == 0) return 0;
-  const unsigned grid = (unsigned)((n + 255) / 256 < 65536 ? (n + 255) / 256 : 65536);
-  if (elem_bytes == 4)
-    hipLaunchKernelGGL(augment_crop<uint32_t>, dim3(grid), dim3(256), 0, st, (const uint32_t *)src, (uint32_t *)dst, B,
-                       C, Hs, Ws, Ho, Wo, params);
-  else if (elem_bytes == 1)
-    hipLaunchKernelGGL(augment_crop<uint8_t>, dim3(grid), dim3(256), 0, st, (const uint8_t *)src, (uint8_t *)dst, B, C,
-                       Hs, Ws, Ho, Wo, params);
-  else
-    return -1;
-  return (int)hipGetLastError();
-}
-
-int launch_pool_swap(void *queue, void *batch, size_t sample_bytes, const int *slots, int b, hipStream_t st) {
-  if (sample_bytes == 0 || b == 0) return 0;
-  const bool wide = sample_bytes % 16 == 0 && ((size_t)queue % 16) == 0 && ((size_t)batch % 16) == 0;
-  const size_t sv = wide ? sample_bytes / 16 : sample_bytes, n = sv * b;
-  const unsigned grid = (unsigned)((n + 255) / 256 < 65536 ? (n + 255) / 256 : 65536);
-  if (wide)
-    hipLaunchKernelGGL(pool_swap<uint4>, dim3(grid), dim3(256), 0, st, (uint4 *)queue, (uint4 *)batch, sv, slots, b);
-  else
-    hipLaunchKernelGGL(pool_swap<uint8_t>, dim3(grid), dim3(256), 0, st, (uint8_t *)queue, (uint8_t *)batch, sv, slots,
-                       b);
-  return (int)hipGetLastError();
 }
 
 // ---------------------------------------------------------------- USM ----
@@ -209,7 +183,7 @@ __global__ __launch_bounds__(256) void usm_pass(const float *src, float *dst, fl
 // cv2.getGaussianKernel(ksize, sigma) as documented (OpenCV imgproc, getGaussianKernel): fixed tables for ksize <= 7
 // with sigma <= 0, else G_i = a exp(-(i - (ksize-1)/2)^2 / (2 sigma^2)) normalised to sum 1, sigma <= 0 meaning
 // 0.3 ((ksize-1) 0.5 - 1) + 0.8; computed in fp64 and rounded once (the reference rounds the fp64 outer product).
-int usm_gaussian_taps(int ksize, double sigma, UsmTaps *out) {
+static int usm_gaussian_taps(int ksize, double sigma, UsmTaps *out) {
   if (ksize < 1 || ksize > USM_MAX_TAPS || !(ksize & 1)) return -1;
   static const double tab1[] = {1.0}, tab3[] = {0.25, 0.5, 0.25}, tab5[] = {0.0625, 0.25, 0.375, 0.25, 0.0625},
                       tab7[] = {0.03125, 0.109375, 0.21875, 0.28125, 0.21875, 0.109375, 0.03125};
@@ -226,37 +200,6 @@ int usm_gaussian_taps(int ksize, double sigma, UsmTaps *out) {
   for (float &v : out->k) v = 0.f;
   for (int i = 0; i < ksize; ++i) out->k[USM_PAD + i] = (float)(fixed ? k[i] : k[i] / sum);
   return 0;
-}
-
-size_t usm_scratch_bytes(int B, int C, int H, int W) { return 3 * sizeof(float) * (size_t)B * C * H * W; }
-
-int launch_usm_sharp(const float *img, float *out, int B, int C, int H, int W, int ksize, float sigma, float weight,
-                     float threshold, void *scratch, hipStream_t st) {
-  UsmTaps taps;
-  if (usm_gaussian_taps(ksize, (double)sigma, &taps)) return -1;
-  const int R = ksize / 2;
-  if (H <= R || W <= R) return -4;   // reflect padding needs pad < size (PyTorch raises the same way)
-  const size_t n = (size_t)B * C * H * W;
-  if (n == 0) return 0;
-  float *t1 = (float *)scratch, *res = t1 + n, *msk = res + n;
-  const dim3 grid_h((unsigned)((W + USM_HTX - 1) / USM_HTX), (unsigned)((H + USM_HTY - 1) / USM_HTY), (unsigned)(B * C));
-  const dim3 grid_v((unsigned)((W + USM_VTX - 1) / USM_VTX), (unsigned)((H + USM_VTY - 1) / USM_VTY), (unsigned)(B * C));
-  const size_t lds_h = sizeof(float) * USM_HTY * ((USM_HTX + 2 * R + 8 + 3) & ~3);
-  const size_t lds_v = sizeof(float) * (USM_VTY + 2 * R) * (USM_VTX + 1);
-  auto run = [&](auto nt) {
-    constexpr int NT = decltype(nt)::value;
-    hipLaunchKernelGGL((usm_pass<false, 0, NT>), grid_h, dim3(256), lds_h, st, img, t1, nullptr, nullptr, nullptr, B * C,
-                       H, W, taps, weight, threshold);
-    hipLaunchKernelGGL((usm_pass<true, 1, NT>), grid_v, dim3(256), lds_v, st, t1, res, msk, img, nullptr, B * C, H, W,
-                       taps, weight, threshold);
-    hipLaunchKernelGGL((usm_pass<false, 0, NT>), grid_h, dim3(256), lds_h, st, msk, t1, nullptr, nullptr, nullptr, B * C,
-                       H, W, taps, weight, threshold);
-    hipLaunchKernelGGL((usm_pass<true, 2, NT>), grid_v, dim3(256), lds_v, st, t1, out, nullptr, img, res, B * C, H, W,
-                       taps, weight, threshold);
-  };
-  if (ksize == 51) run(std::integral_constant<int, 51>{});
-  else run(std::integral_constant<int, 0>{});
-  return (int)hipGetLastError();
 }
 
 // ------------------------------------------------------------ filter2D ----
@@ -327,17 +270,6 @@ __global__ __launch_bounds__(256) void filter2d_kernel(const float *img, const f
       if (x + j < W) out[plane + (size_t)y * W + x + j] = acc[j];
 }
 
-int launch_filter2d(const float *img, const float *kernels, float *out, int B, int C, int H, int W, int k, int nk,
-                    hipStream_t st) {
-  if (k < 1 || k > 21 || !(k & 1) || (nk != 1 && nk != B)) return -1;
-  if (H <= k / 2 || W <= k / 2) return -4;
-  if ((size_t)B * C * H * W == 0) return 0;
-  const dim3 grid((unsigned)((W + 63) / 64), (unsigned)((H + 15) / 16), (unsigned)(B * C));
-  if (k <= 9) hipLaunchKernelGGL((filter2d_kernel<9>), grid, dim3(256), 0, st, img, kernels, out, C, H, W, k, nk);
-  else hipLaunchKernelGGL((filter2d_kernel<21>), grid, dim3(256), 0, st, img, kernels, out, C, H, W, k, nk);
-  return (int)hipGetLastError();
-}
-
 // ---------------------------------------------------------------- JPEG ----
 // DiffJPEG(differentiable=False).forward (basicsr/utils/diffjpeg.py:449-487), the JPEG simulation of the degradation
 // chain (realesrganssl_model.py:34,201,240,285,290): zero-pad to multiples of 16, x 255, RGB -> YCbCr (:49-70), 2 x 2
@@ -371,7 +303,7 @@ __global__ __launch_bounds__(64) void jpeg_kernel(const float *img, float *out, 
   const float *src = img + (size_t)b * 3 * plane;
   // tensor branch (diffjpeg.py:475-476): quality_to_factor on fp32 tensor elements, two fp32 roundings.  Scalar
   // branch (:473-474): Python doubles, rounded to fp32 ONCE where the table is multiplied (:169,199) -- that factor
-  // is formed on the host in double (launch_jpeg) and arrives as `factor_host`.
+  // is formed on the host in double (ssg_diffjpeg) and arrives as `factor_host`.
   float factor = factor_host;
   if (quality) {
     float q = quality[b];
@@ -460,16 +392,108 @@ __global__ __launch_bounds__(64) void jpeg_kernel(const float *img, float *out, 
   }
 }
 
-int launch_jpeg(const float *img, float *out, int B, int H, int W, const float *quality_dev, float quality_host,
-                hipStream_t st) {
-  if ((size_t)B * H * W == 0) return 0;
-  const dim3 grid((unsigned)((W + 15) / 16), (unsigned)((H + 15) / 16), (unsigned)B);
-  // scalar quality: quality_to_factor (diffjpeg.py:32-45) in double like the reference's Python floats, one rounding
-  double q = (double)quality_host;
-  q = q < 50.0 ? 5000.0 / q : 200.0 - q * 2.0;
-  const float factor_host = (float)(q / 100.0);
-  hipLaunchKernelGGL(jpeg_kernel, grid, dim3(64), 0, st, img, out, H, W, quality_dev, factor_host);
+}  // namespace ssg
+
+// ---- (E) the entry points: every refusal is decided here, before the launch ----
+using namespace ssg;
+
+extern "C" {
+
+int ssg_augment_crop(const void *src, void *dst, int elem_bytes, int B, int C, int Hs, int Ws, int Ho, int Wo,
+                     const int *params, ssg_stream_t stream) {
+  if (!src || !dst || !params || B < 0 || C <= 0 || Hs <= 0 || Ws <= 0 || Ho <= 0 || Wo <= 0 ||
+      (elem_bytes != 1 && elem_bytes != 4))
+    return SSG_E_BADARG;
+  const size_t n = (size_t)B * C * Ho * Wo;
+  if (n == 0) return 0;
+  const unsigned grid = (unsigned)((n + 255) / 256 < 65536 ? (n + 255) / 256 : 65536);
+  hipStream_t st = (hipStream_t)stream;
+  if (elem_bytes == 4)
+    hipLaunchKernelGGL(augment_crop<uint32_t>, dim3(grid), dim3(256), 0, st, (const uint32_t *)src, (uint32_t *)dst, B,
+                       C, Hs, Ws, Ho, Wo, params);
+  else
+    hipLaunchKernelGGL(augment_crop<uint8_t>, dim3(grid), dim3(256), 0, st, (const uint8_t *)src, (uint8_t *)dst, B, C,
+                       Hs, Ws, Ho, Wo, params);
   return (int)hipGetLastError();
 }
 
-}  // namespace ssg
+int ssg_pool_swap(void *queue, void *batch, size_t sample_bytes, const int *slots, int b, ssg_stream_t stream) {
+  if (!queue || !batch || !slots || b < 0) return SSG_E_BADARG;
+  if (sample_bytes == 0 || b == 0) return 0;
+  const bool wide = sample_bytes % 16 == 0 && !unaligned(queue, 16) && !unaligned(batch, 16);
+  const size_t sv = wide ? sample_bytes / 16 : sample_bytes, n = sv * b;
+  const unsigned grid = (unsigned)((n + 255) / 256 < 65536 ? (n + 255) / 256 : 65536);
+  hipStream_t st = (hipStream_t)stream;
+  if (wide)
+    hipLaunchKernelGGL(pool_swap<uint4>, dim3(grid), dim3(256), 0, st, (uint4 *)queue, (uint4 *)batch, sv, slots, b);
+  else
+    hipLaunchKernelGGL(pool_swap<uint8_t>, dim3(grid), dim3(256), 0, st, (uint8_t *)queue, (uint8_t *)batch, sv, slots,
+                       b);
+  return (int)hipGetLastError();
+}
+
+size_t ssg_usm_scratch_bytes(int B, int C, int H, int W) { return 3 * sizeof(float) * (size_t)B * C * H * W; }
+
+int ssg_usm_sharp(const float *img, float *out, int B, int C, int H, int W, int radius, float sigma, float weight,
+                  float threshold, void *scratch, size_t scratch_bytes, ssg_stream_t stream) {
+  if (B < 0 || C <= 0 || H <= 0 || W <= 0 || radius < 0) return SSG_E_BADARG;
+  if (B == 0) return 0;
+  if (!img || !out || !scratch || img == out) return SSG_E_BADARG;
+  if (scratch_bytes < ssg_usm_scratch_bytes(B, C, H, W)) return SSG_E_WORKSPACE;
+  const int ksize = radius % 2 == 0 ? radius + 1 : radius;   // img_process_util.py:67-68
+  UsmTaps taps;
+  if (usm_gaussian_taps(ksize, (double)sigma, &taps)) return SSG_E_BADARG;
+  const int R = ksize / 2;
+  if (H <= R || W <= R) return SSG_E_IMAGESMALL;   // reflect padding needs pad < size (PyTorch raises the same way)
+  const size_t n = (size_t)B * C * H * W;
+  float *t1 = (float *)scratch, *res = t1 + n, *msk = res + n;
+  const dim3 grid_h((unsigned)((W + USM_HTX - 1) / USM_HTX), (unsigned)((H + USM_HTY - 1) / USM_HTY), (unsigned)(B * C));
+  const dim3 grid_v((unsigned)((W + USM_VTX - 1) / USM_VTX), (unsigned)((H + USM_VTY - 1) / USM_VTY), (unsigned)(B * C));
+  const size_t lds_h = sizeof(float) * USM_HTY * ((USM_HTX + 2 * R + 8 + 3) & ~3);
+  const size_t lds_v = sizeof(float) * (USM_VTY + 2 * R) * (USM_VTX + 1);
+  hipStream_t st = (hipStream_t)stream;
+  auto run = [&](auto nt) {
+    constexpr int NT = decltype(nt)::value;
+    hipLaunchKernelGGL((usm_pass<false, 0, NT>), grid_h, dim3(256), lds_h, st, img, t1, nullptr, nullptr, nullptr, B * C,
+                       H, W, taps, weight, threshold);
+    hipLaunchKernelGGL((usm_pass<true, 1, NT>), grid_v, dim3(256), lds_v, st, t1, res, msk, img, nullptr, B * C, H, W,
+                       taps, weight, threshold);
+    hipLaunchKernelGGL((usm_pass<false, 0, NT>), grid_h, dim3(256), lds_h, st, msk, t1, nullptr, nullptr, nullptr, B * C,
+                       H, W, taps, weight, threshold);
+    hipLaunchKernelGGL((usm_pass<true, 2, NT>), grid_v, dim3(256), lds_v, st, t1, out, nullptr, img, res, B * C, H, W,
+                       taps, weight, threshold);
+  };
+  if (ksize == 51) run(std::integral_constant<int, 51>{});
+  else run(std::integral_constant<int, 0>{});
+  return (int)hipGetLastError();
+}
+
+int ssg_filter2d(const float *img, const float *kernels, float *out, int B, int C, int H, int W, int k, int n_kernels,
+                 ssg_stream_t stream) {
+  if (B < 0 || C <= 0 || H <= 0 || W <= 0) return SSG_E_BADARG;
+  if (B == 0) return 0;
+  if (!img || !kernels || !out || img == out) return SSG_E_BADARG;
+  if (k < 1 || k > 21 || !(k & 1) || (n_kernels != 1 && n_kernels != B)) return SSG_E_BADARG;
+  if (H <= k / 2 || W <= k / 2) return SSG_E_IMAGESMALL;
+  const dim3 grid((unsigned)((W + 63) / 64), (unsigned)((H + 15) / 16), (unsigned)(B * C));
+  hipStream_t st = (hipStream_t)stream;
+  if (k <= 9) hipLaunchKernelGGL((filter2d_kernel<9>), grid, dim3(256), 0, st, img, kernels, out, C, H, W, k, n_kernels);
+  else hipLaunchKernelGGL((filter2d_kernel<21>), grid, dim3(256), 0, st, img, kernels, out, C, H, W, k, n_kernels);
+  return (int)hipGetLastError();
+}
+
+int ssg_diffjpeg(const float *img, float *out, int B, int H, int W, const float *quality_dev, float quality,
+                 ssg_stream_t stream) {
+  if (B < 0 || H <= 0 || W <= 0) return SSG_E_BADARG;
+  if (B == 0) return 0;
+  if (!img || !out || (!quality_dev && !(quality > 0.f))) return SSG_E_BADARG;
+  const dim3 grid((unsigned)((W + 15) / 16), (unsigned)((H + 15) / 16), (unsigned)B);
+  // scalar quality: quality_to_factor (diffjpeg.py:32-45) in double like the reference's Python floats, one rounding
+  double q = (double)quality;
+  q = q < 50.0 ? 5000.0 / q : 200.0 - q * 2.0;
+  const float factor_host = (float)(q / 100.0);
+  hipLaunchKernelGGL(jpeg_kernel, grid, dim3(64), 0, (hipStream_t)stream, img, out, H, W, quality_dev, factor_host);
+  return (int)hipGetLastError();
+}
+
+}  // extern "C"

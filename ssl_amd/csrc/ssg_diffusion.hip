@@ -34,7 +34,8 @@
 // walk: its threads take the groups of four by their index inside the chunk, whatever the alignment (scalar loads
 // where the chunk is not on a 16-byte boundary), so that S_b does not depend on where the sample lies: sample b of a
 // batch gives the bits of that sample alone.  One writer per output element, no atomics, no scratch; LDS holds the
-// folds only.  The launchers trust their arguments: the entry points in ssg_api.hip refuse bad ones.
+// folds only.
+// This file defines the ten entry points ssg_diff_*, at its end: they refuse bad arguments before any launch.
 #include "ssg_chunked.hpp"
 
 namespace ssg {
@@ -315,28 +316,61 @@ static unsigned flat_grid(size_t total) {
   return (unsigned)(want < 1 ? 1 : (want > (size_t)tuning.grid_cap ? (size_t)tuning.grid_cap : want));
 }
 
-}  // namespace diff
-
-int diff_chunk() { return diff::tuning.chunk; }
-
-int diff_grid_cap() { return diff::tuning.grid_cap; }
-
 // the chunks of a sample and of the call; false where the call's count does not fit an int
-bool diff_chunks(size_t B, size_t n, size_t *per_sample, size_t *total) {
-  const size_t cps = chunked::chunks_of(n, (size_t)diff::tuning.chunk);
+static bool chunks(size_t B, size_t n, size_t *per_sample, size_t *total) {
+  const size_t cps = chunks_of(n, (size_t)tuning.chunk);
   if (B == 0 || cps == 0 || cps > (size_t)INT_MAX / B) return false;
   *per_sample = cps, *total = cps * B;
   return true;
 }
 
-int launch_diff_combine(const float *x, const float *y, const long long *t, const float *A, const float *Bt, int T,
-                        size_t B, size_t n, int subtract, int clamp, float lo, float hi, float *out, hipStream_t st) {
-  using namespace diff;
+// what every per-sample entry point checks of its shape: (B, n) with a chunk count that fits, a table of T entries
+static int check_shape(size_t B, size_t n, int T, size_t *per_sample, size_t *total) {
+  if (B < 1 || n < 1 || T < 1) return SSG_E_BADARG;
+  return chunks(B, n, per_sample, total) ? 0 : SSG_E_TOOLARGE;
+}
+
+// the canvas (B, C, h, w), its tiles of (C, ts, ts) and the n_tiles of them in a tile tensor: each below 2^31 elements
+static int check_canvas(int ntiles, int B, int C, int h, int w, int ts, long long n_tiles) {
+  if (ntiles < 1 || B < 1 || C < 1 || h < 1 || w < 1 || ts < 1 || ts > h || ts > w || n_tiles < 1) return SSG_E_BADARG;
+  const unsigned long long lim = 1ull << 31;
+  if ((unsigned long long)B * C >= lim || (unsigned long long)B * C * h >= lim || (unsigned long long)B * C * h * w >= lim)
+    return SSG_E_TOOLARGE;
+  if ((unsigned long long)C * ts * ts >= lim || (unsigned long long)n_tiles * C * ts * ts >= lim) return SSG_E_TOOLARGE;
+  return 0;
+}
+
+}  // namespace diff
+
+}  // namespace ssg
+
+// ---- (W) the entry points: every refusal is decided here, before the launch ----
+using namespace ssg;
+using namespace ssg::diff;
+
+extern "C" {
+
+int ssg_diff_chunk(void) { return tuning.chunk; }
+
+int ssg_diff_grid_cap(void) { return tuning.grid_cap; }
+
+size_t ssg_diff_workspace_bytes(size_t B, size_t n) {
   size_t cps = 0, total = 0;
-  if (!diff_chunks(B, n, &cps, &total)) return SSG_E_TOOLARGE;
+  return chunks(B, n, &cps, &total) ? sizeof(double) * total : 0;
+}
+
+int ssg_diff_combine(const float *x, const float *y, const long long *t, const float *A, const float *Bt, int T,
+                     size_t B, size_t n, int subtract, int clamp, float lo, float hi, float *out, ssg_stream_t stream) {
+  size_t cps = 0, total = 0;
+  if (!x || !y || !t || !A || !Bt || !out) return SSG_E_BADARG;
+  if (clamp && !(lo <= hi)) return SSG_E_BADARG;   // (a NaN fails the comparison)
+  if (const int rc = check_shape(B, n, T, &cps, &total)) return rc;
+  if (unaligned(x, 4) || unaligned(y, 4) || unaligned(A, 4) || unaligned(Bt, 4) || unaligned(out, 4) || unaligned(t, 8))
+    return SSG_E_ALIGN;
   const auto go = [&](auto sub, auto cl) {
     hipLaunchKernelGGL((combine_kernel<decltype(sub)::value, decltype(cl)::value>), dim3(grid_of(total, tuning)),
-                       dim3(NT), 0, st, x, y, t, A, Bt, T, total, cps, n, (unsigned)tuning.chunk, lo, hi, out);
+                       dim3(NT), 0, (hipStream_t)stream, x, y, t, A, Bt, T, total, cps, n, (unsigned)tuning.chunk, lo, hi,
+                       out);
   };
   if (subtract && clamp) go(std::true_type{}, std::true_type{});
   else if (subtract) go(std::true_type{}, std::false_type{});
@@ -345,16 +379,21 @@ int launch_diff_combine(const float *x, const float *y, const long long *t, cons
   return (int)hipGetLastError();
 }
 
-int launch_diff_p_sample(const float *x, const float *model_out, const float *noise, const long long *t,
-                         const float *ra, const float *rb, const float *c1, const float *c2, const float *sigma, int T,
-                         size_t B, size_t n, int param, int clip, float *out, float *x0_out, hipStream_t st) {
-  using namespace diff;
+int ssg_diff_p_sample(const float *x, const float *model_out, const float *noise, const long long *t, const float *ra,
+                      const float *rb, const float *c1, const float *c2, const float *sigma, int T, size_t B, size_t n,
+                      int param, int clip, float *out, float *x0_out, ssg_stream_t stream) {
   size_t cps = 0, total = 0;
-  if (!diff_chunks(B, n, &cps, &total)) return SSG_E_TOOLARGE;
+  if (!x || !model_out || !noise || !t || !c1 || !c2 || !sigma || !out) return SSG_E_BADARG;
+  if (param < SSG_DIFF_EPS || param > SSG_DIFF_V || (param != SSG_DIFF_X0 && (!ra || !rb))) return SSG_E_BADARG;
+  if (const int rc = check_shape(B, n, T, &cps, &total)) return rc;
+  if (unaligned(x, 4) || unaligned(model_out, 4) || unaligned(noise, 4) || unaligned(ra, 4) || unaligned(rb, 4) ||
+      unaligned(c1, 4) || unaligned(c2, 4) || unaligned(sigma, 4) || unaligned(out, 4) || unaligned(x0_out, 4) ||
+      unaligned(t, 8))
+    return SSG_E_ALIGN;
   const auto go = [&](auto pm, auto cl, auto x0) {
     hipLaunchKernelGGL((p_sample_kernel<decltype(pm)::value, decltype(cl)::value, decltype(x0)::value>),
-                       dim3(grid_of(total, tuning)), dim3(NT), 0, st, x, model_out, noise, t, ra, rb, c1, c2, sigma, T,
-                       total, cps, n, (unsigned)tuning.chunk, out, x0_out);
+                       dim3(grid_of(total, tuning)), dim3(NT), 0, (hipStream_t)stream, x, model_out, noise, t, ra, rb, c1,
+                       c2, sigma, T, total, cps, n, (unsigned)tuning.chunk, out, x0_out);
   };
   const auto with_flags = [&](auto pm) {
     if (clip && x0_out) go(pm, std::true_type{}, std::true_type{});
@@ -368,40 +407,54 @@ int launch_diff_p_sample(const float *x, const float *model_out, const float *no
   return (int)hipGetLastError();
 }
 
-int launch_diff_loss_sums(const float *pred, const float *target, size_t B, size_t n, int kind, void *workspace,
-                          hipStream_t st) {
-  using namespace diff;
+int ssg_diff_loss_sums(const float *pred, const float *target, size_t B, size_t n, int kind, void *workspace,
+                       size_t workspace_bytes, ssg_stream_t stream) {
   size_t cps = 0, total = 0;
-  if (!diff_chunks(B, n, &cps, &total)) return SSG_E_TOOLARGE;
+  if (!pred || !target || !workspace || (kind != SSG_PIX_L1 && kind != SSG_PIX_MSE)) return SSG_E_BADARG;
+  if (const int rc = check_shape(B, n, 1, &cps, &total)) return rc;
+  if (workspace_bytes < sizeof(double) * total) return SSG_E_WORKSPACE;
+  if (unaligned(pred, 4) || unaligned(target, 4) || unaligned(workspace, 8)) return SSG_E_ALIGN;
   const auto go = [&](auto kd) {
-    hipLaunchKernelGGL(loss_sums_kernel<decltype(kd)::value>, dim3(grid_of(total, tuning)), dim3(NT), 0, st, pred,
-                       target, total, cps, n, (unsigned)tuning.chunk, (double *)workspace);
+    hipLaunchKernelGGL(loss_sums_kernel<decltype(kd)::value>, dim3(grid_of(total, tuning)), dim3(NT), 0,
+                       (hipStream_t)stream, pred, target, total, cps, n, (unsigned)tuning.chunk, (double *)workspace);
   };
   if (kind == SSG_PIX_L1) go(std::integral_constant<int, SSG_PIX_L1>{});
   else go(std::integral_constant<int, SSG_PIX_MSE>{});
   return (int)hipGetLastError();
 }
 
-int launch_diff_loss_finish(const void *workspace, const long long *t, const float *p2, const float *logvar,
-                            const float *lvlb, int T, size_t B, size_t n, double lsw, double elbo, double *sums_out,
-                            double *scalars_out, double *coef_out, double *dlogvar_out, hipStream_t st) {
-  using namespace diff;
+int ssg_diff_loss_finish(const void *workspace, size_t workspace_bytes, const long long *t, const float *p2,
+                         const float *logvar, const float *lvlb, int T, size_t B, size_t n, double l_simple_weight,
+                         double original_elbo_weight, double *sums_out, double *scalars_out, double *coef_out,
+                         double *dlogvar_out, ssg_stream_t stream) {
   size_t cps = 0, total = 0;
-  if (!diff_chunks(B, n, &cps, &total)) return SSG_E_TOOLARGE;
-  hipLaunchKernelGGL(loss_finish_kernel, dim3(1), dim3(NT), 0, st, (const double *)workspace, cps, t, p2, logvar, lvlb,
-                     T, (int)B, (double)n, lsw, elbo, sums_out, scalars_out, coef_out, dlogvar_out);
+  if (!workspace || !t || !logvar || !lvlb || !sums_out || !scalars_out || !coef_out) return SSG_E_BADARG;
+  if (l_simple_weight != l_simple_weight || original_elbo_weight != original_elbo_weight) return SSG_E_BADARG;
+  if (const int rc = check_shape(B, n, T, &cps, &total)) return rc;
+  if (B > (size_t)INT_MAX) return SSG_E_TOOLARGE;
+  if (workspace_bytes < sizeof(double) * total) return SSG_E_WORKSPACE;
+  if (unaligned(workspace, 8) || unaligned(t, 8) || unaligned(p2, 4) || unaligned(logvar, 4) || unaligned(lvlb, 4) ||
+      unaligned(sums_out, 8) || unaligned(scalars_out, 8) || unaligned(coef_out, 8) || unaligned(dlogvar_out, 8))
+    return SSG_E_ALIGN;
+  hipLaunchKernelGGL(loss_finish_kernel, dim3(1), dim3(NT), 0, (hipStream_t)stream, (const double *)workspace, cps, t, p2,
+                     logvar, lvlb, T, (int)B, (double)n, l_simple_weight, original_elbo_weight, sums_out, scalars_out,
+                     coef_out, dlogvar_out);
   return (int)hipGetLastError();
 }
 
-int launch_diff_loss_grad(const float *pred, const float *target, const float *grad_x0, const long long *t,
-                          const float *rb, int T, const float *g, const double *coef, size_t B, size_t n, int kind,
-                          float *grad_pred, hipStream_t st) {
-  using namespace diff;
+int ssg_diff_loss_grad(const float *pred, const float *target, const float *grad_x0, const long long *t,
+                       const float *rb, int T, const float *g, const double *coef, size_t B, size_t n, int kind,
+                       float *grad_pred, ssg_stream_t stream) {
   size_t cps = 0, total = 0;
-  if (!diff_chunks(B, n, &cps, &total)) return SSG_E_TOOLARGE;
+  if (!pred || !target || !g || !coef || !grad_pred || (kind != SSG_PIX_L1 && kind != SSG_PIX_MSE)) return SSG_E_BADARG;
+  if (grad_x0 && (!t || !rb)) return SSG_E_BADARG;
+  if (const int rc = check_shape(B, n, grad_x0 ? T : 1, &cps, &total)) return rc;
+  if (unaligned(pred, 4) || unaligned(target, 4) || unaligned(grad_x0, 4) || unaligned(rb, 4) || unaligned(g, 4) ||
+      unaligned(grad_pred, 4) || unaligned(t, 8) || unaligned(coef, 8))
+    return SSG_E_ALIGN;
   const auto go = [&](auto kd, auto x0) {
     hipLaunchKernelGGL((loss_grad_kernel<decltype(kd)::value, decltype(x0)::value>), dim3(grid_of(total, tuning)),
-                       dim3(NT), 0, st, pred, target, grad_x0, t, rb, T, g, coef, total, cps, n,
+                       dim3(NT), 0, (hipStream_t)stream, pred, target, grad_x0, t, rb, T, g, coef, total, cps, n,
                        (unsigned)tuning.chunk, grad_pred);
   };
   const auto with_x0 = [&](auto kd) {
@@ -413,24 +466,29 @@ int launch_diff_loss_grad(const float *pred, const float *target, const float *g
   return (int)hipGetLastError();
 }
 
-int launch_diff_canvas_gather(const float *src, const int *tiles, int ntiles, int B, int C, int h, int w, int ts,
-                              float *out, hipStream_t st) {
-  using namespace diff;
+int ssg_diff_canvas_gather(const float *src, const int *tiles, int ntiles, int B, int C, int h, int w, int ts,
+                           float *out, ssg_stream_t stream) {
+  if (!src || !tiles || !out) return SSG_E_BADARG;
+  if (const int rc = check_canvas(ntiles, B, C, h, w, ts, (long long)ntiles * B)) return rc;
+  if (unaligned(src, 4) || unaligned(tiles, 4) || unaligned(out, 4)) return SSG_E_ALIGN;
   const Canvas cv = {B, C, h, w, ts, ntiles};
   const size_t total = (size_t)ntiles * B * C * ts * ts;
-  hipLaunchKernelGGL(canvas_gather_kernel, dim3(flat_grid(total)), dim3(NT), 0, st, src, tiles, cv, total, out);
+  hipLaunchKernelGGL(canvas_gather_kernel, dim3(flat_grid(total)), dim3(NT), 0, (hipStream_t)stream, src, tiles, cv, total,
+                     out);
   return (int)hipGetLastError();
 }
 
-int launch_diff_canvas_stitch(const float *preds, int n_preds, int bstep, const int *tiles, int ntiles,
-                              const double *weights, size_t wsb, size_t wsc, int B, int C, int h, int w, int ts,
-                              float *out, hipStream_t st) {
-  using namespace diff;
+int ssg_diff_canvas_stitch(const float *preds, int n_preds, int bstep, const int *tiles, int ntiles,
+                           const double *weights, size_t wsb, size_t wsc, int B, int C, int h, int w, int ts,
+                           float *out, ssg_stream_t stream) {
+  if (!preds || !tiles || !out || (bstep != 0 && bstep != 1)) return SSG_E_BADARG;
+  if (const int rc = check_canvas(ntiles, B, C, h, w, ts, n_preds)) return rc;
+  if (unaligned(preds, 4) || unaligned(tiles, 4) || unaligned(out, 4) || unaligned(weights, 8)) return SSG_E_ALIGN;
   const Canvas cv = {B, C, h, w, ts, ntiles};
   const size_t total = (size_t)B * C * h * w;
-  hipLaunchKernelGGL(canvas_stitch_kernel, dim3(flat_grid(total)), dim3(NT), 0, st, preds, tiles, weights, cv, n_preds,
-                     bstep, wsb, wsc, total, out);
+  hipLaunchKernelGGL(canvas_stitch_kernel, dim3(flat_grid(total)), dim3(NT), 0, (hipStream_t)stream, preds, tiles, weights,
+                     cv, n_preds, bstep, wsb, wsc, total, out);
   return (int)hipGetLastError();
 }
 
-}  // namespace ssg
+}  // extern "C"

@@ -930,7 +930,7 @@ static size_t n_strips(int B, int H, int W) { return (size_t)B * ((H + STRIP_ROW
 // n_super_tiles), then the k_s 49 forward's strip list (count, then n_strips (strip id, first place) pairs), then
 // (capacity) the tile-major order of the rows left to the direct kernels
 constexpr int PLAN_HDR_WORDS = 4;
-int fwd_plan_strip_offset(int B, int H, int W) { return PLAN_HDR_WORDS + (int)n_super_tiles(B, H, W); }
+static int fwd_plan_strip_offset(int B, int H, int W) { return PLAN_HDR_WORDS + (int)n_super_tiles(B, H, W); }
 int fwd_plan_order_offset(int B, int H, int W) { return fwd_plan_strip_offset(B, H, W) + 1 + 2 * (int)n_strips(B, H, W); }
 PlanView plan_view(const int *plan, int B, int H, int W) {
   return PlanView{plan, plan + 1, plan + PLAN_HDR_WORDS, plan + fwd_plan_strip_offset(B, H, W),

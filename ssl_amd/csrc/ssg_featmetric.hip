@@ -228,8 +228,6 @@ __global__ __launch_bounds__(NT) void dists_finish_kernel(const DistsSet s, cons
 }
 
 // ---- host ----
-inline bool unaligned(size_t p, size_t a) { return p % a != 0; }
-
 // what both entry points check of the shapes: K, N, C, H, W; fills hw[k]
 static int check_shapes(int K, int N, const int *C, const int *H, const int *W, size_t *hw) {
   if (K < 1 || K > MAX_LAYERS || N < 1 || !C || !H || !W) return SSG_E_BADARG;
@@ -289,19 +287,19 @@ constexpr Tuning tuning = {CHUNK, GRID_CAP};
 
 }  // namespace featmetric
 
-int featmetric_grid_cap() { return featmetric::GRID_CAP; }
-int featmetric_unit() { return featmetric::UNIT; }
-int featmetric_chunk() { return featmetric::CHUNK; }
+static int featmetric_grid_cap() { return featmetric::GRID_CAP; }
+static int featmetric_unit() { return featmetric::UNIT; }
+static int featmetric_chunk() { return featmetric::CHUNK; }
 
-int launch_lpips_layers(const featmetric::LpipsSet &s, void *workspace, double *out, hipStream_t st) {
+static int launch_lpips_layers(const featmetric::LpipsSet &s, void *workspace, double *out, hipStream_t st) {
   using namespace featmetric;
   hipLaunchKernelGGL(lpips_kernel, dim3(grid_of(s.n_units, tuning)), dim3(NT), 0, st, s, (double *)workspace);
   hipLaunchKernelGGL(lpips_fold_kernel, dim3((unsigned)s.N), dim3(NT), 0, st, s, (const double *)workspace, out);
   return (int)hipGetLastError();
 }
 
-int launch_dists_score(const featmetric::DistsSet &s, const float *alpha, const float *beta, void *workspace, double *out,
-                       hipStream_t st) {
+static int launch_dists_score(const featmetric::DistsSet &s, const float *alpha, const float *beta, void *workspace, double *out,
+                              hipStream_t st) {
   using namespace featmetric;
   hipLaunchKernelGGL(dists_moments_kernel, dim3(grid_of(s.n_chunks, tuning)), dim3(NT), 0, st, s, (double *)workspace);
   hipLaunchKernelGGL(dists_finish_kernel, dim3((unsigned)s.N), dim3(NT), 0, st, s, (const double *)workspace, alpha,
@@ -339,7 +337,7 @@ int ssg_lpips_layers(int n_layers, int n_images, const size_t *f0, const size_t 
     if (!f0[k] || !f1[k] || !w[k]) return SSG_E_BADARG;
   }
   if (workspace_bytes < sizeof(double) * (size_t)s.n_units) return SSG_E_WORKSPACE;
-  if (unaligned((size_t)workspace, 8) || unaligned((size_t)out, 8)) return SSG_E_ALIGN;
+  if (unaligned(workspace, 8) || unaligned(out, 8)) return SSG_E_ALIGN;
   for (int k = 0; k < s.K; ++k) {
     if (unaligned(f0[k], 4) || unaligned(f1[k], 4) || unaligned(w[k], 4)) return SSG_E_ALIGN;
     s.l[k].f0 = (const float *)f0[k], s.l[k].f1 = (const float *)f1[k], s.l[k].w = (const float *)w[k];
@@ -364,8 +362,8 @@ int ssg_dists_score(int n_layers, int n_images, const size_t *x, const size_t *y
     if (!x[k] || !y[k]) return SSG_E_BADARG;
   }
   if (workspace_bytes < 5 * sizeof(double) * (size_t)s.n_chunks) return SSG_E_WORKSPACE;
-  if (unaligned((size_t)workspace, 8) || unaligned((size_t)out, 8) || unaligned((size_t)alpha, 4) ||
-      unaligned((size_t)beta, 4))
+  if (unaligned(workspace, 8) || unaligned(out, 8) || unaligned(alpha, 4) ||
+      unaligned(beta, 4))
     return SSG_E_ALIGN;
   for (int k = 0; k < s.K; ++k) {
     if (unaligned(x[k], 4) || unaligned(y[k], 4)) return SSG_E_ALIGN;

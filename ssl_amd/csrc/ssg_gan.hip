@@ -21,7 +21,8 @@
 // Two streaming kernels on ssg_stream.hpp's walk of x and its launch geometry; the gradient is stored 16 bytes wide where
 // grad shares x's alignment; where it does not, x and grad are both taken one by one.  A call of a single workgroup
 // (n <= 1,024) writes sums_out itself.
-// The launchers trust their arguments: the entry points in ssg_api.hip refuse bad ones before any launch.
+// This file defines the entry points ssg_gan_workspace_bytes, ssg_gan_grid_cap, ssg_gan_sums and ssg_gan_grad, at its end:
+// they refuse bad arguments before any launch.
 #include <math.h>
 
 #include <type_traits>
@@ -127,15 +128,32 @@ inline void with_kind(int kind, F f) {
   }
 }
 
+// what both entry points check of the logits
+static int gan_check(const float *x, size_t n, int kind, float sign) {
+  if (!x || n == 0 || kind < SSG_GAN_BCE || kind > SSG_GAN_HINGE || !(sign == 1.f || sign == -1.f)) return SSG_E_BADARG;
+  return unaligned(x, 4) ? SSG_E_ALIGN : 0;   // (the head / float4 split assumes a float's own alignment)
+}
+
 }  // namespace gan
 
-int gan_grid_cap() { return gan::MAX_WG; }
+}  // namespace ssg
 
-size_t gan_workspace_bytes() { return sizeof(double) * 2 * gan::MAX_WG; }
+// ---- (Q) the entry points: every refusal is decided here, before the launch ----
+using namespace ssg;
 
-int launch_gan_sums(const float *x, size_t n, int kind, float sign, float label, const float *shift, void *workspace,
-                    double *sums_out, hipStream_t st) {
+extern "C" {
+
+size_t ssg_gan_workspace_bytes(void) { return sizeof(double) * 2 * gan::MAX_WG; }
+
+int ssg_gan_grid_cap(void) { return gan::MAX_WG; }
+
+int ssg_gan_sums(const float *x, size_t n, int kind, float sign, float label, const float *shift, void *workspace,
+                 double *sums_out, ssg_stream_t stream) {
   using namespace gan;
+  if (const int rc = gan_check(x, n, kind, sign)) return rc;
+  if (!workspace || !sums_out) return SSG_E_BADARG;
+  if (unaligned(workspace, 8) || unaligned(sums_out, 8)) return SSG_E_ALIGN;
+  hipStream_t st = (hipStream_t)stream;
   const unsigned grid = grid_for(n, EPT);
   double *part = partials_of(grid, workspace, sums_out);
   with_kind(kind, [&](auto k) {
@@ -144,14 +162,17 @@ int launch_gan_sums(const float *x, size_t n, int kind, float sign, float label,
   return finish_sums<2>(grid, part, sums_out, st);
 }
 
-int launch_gan_grad(const float *x, size_t n, int kind, float sign, float label, const float *shift, const double *coef,
-                    float *grad, hipStream_t st) {
+int ssg_gan_grad(const float *x, size_t n, int kind, float sign, float label, const float *shift, const double *coef,
+                 float *grad, ssg_stream_t stream) {
   using namespace gan;
+  if (const int rc = gan_check(x, n, kind, sign)) return rc;
+  if (!coef || !grad) return SSG_E_BADARG;
+  if (unaligned(coef, 8) || unaligned(grad, 4)) return SSG_E_ALIGN;
   with_kind(kind, [&](auto k) {
-    hipLaunchKernelGGL(gan_grad_kernel<decltype(k)::value>, dim3(grid_for(n, EPT)), dim3(NT), 0, st, x, n, sign, label,
-                       shift, coef, grad);
+    hipLaunchKernelGGL(gan_grad_kernel<decltype(k)::value>, dim3(grid_for(n, EPT)), dim3(NT), 0, (hipStream_t)stream, x, n,
+                       sign, label, shift, coef, grad);
   });
   return (int)hipGetLastError();
 }
 
-}  // namespace ssg
+}  // extern "C"

@@ -17,6 +17,9 @@
 // Rows that live in the tile-major region of a k_s = 49 call (negative row scale) are not touched by ssg_grad_rows:
 // ssg_rows_tm (fused step) / ssg_rows_tm_mat (materialising call: it also writes the normalised SSG rows) below walk
 // them with lanes = pixels, and the dense backward forms their G itself.
+//
+// The two criteria on tensors that already exist live here too, with their entry points ssg_criteria_scratch_bytes,
+// ssg_criteria_sums and ssg_criteria_grad at the end of the file.
 #include "ssg_stream.hpp"
 
 namespace ssg {
@@ -624,22 +627,15 @@ __global__ __launch_bounds__(256) void criteria_grad_kernel(const float *a, cons
   }
 }
 
-size_t criteria_scratch_bytes() { return sizeof(double) * 2 * CRIT_GRID; }
-
-int launch_criteria_sums(const float *a, const float *b, size_t n, void *scratch, float *sums_out, hipStream_t st) {
+// (file-local, in front of launch_grad_rows: the order in which this file first names its kernel templates is the order
+// of the kernels in the code object)
+static int criteria_sums(const float *a, const float *b, size_t n, void *scratch, float *sums_out, hipStream_t st) {
   const size_t want = (n / 4 + 255) / 256;
   const unsigned grid = (unsigned)(want < 1 ? 1 : (want > CRIT_GRID ? CRIT_GRID : want));
   hipLaunchKernelGGL(criteria_sums_kernel, dim3(grid), dim3(256), 0, st, a, b, n, (double *)scratch);
   // (always folded, a single workgroup's pair included: the partials are fp64 in the scratch, the result is fp32)
   hipLaunchKernelGGL((stream::fold_kernel<2, float>), dim3(1), dim3(256), 0, st, (const double *)scratch, (int)grid,
                      sums_out);
-  return (int)hipGetLastError();
-}
-
-int launch_criteria_grad(const float *a, const float *b, size_t n, const float *coef, float *g, hipStream_t st) {
-  const size_t want = (n / 4 + 255) / 256;
-  const unsigned grid = (unsigned)(want < 1 ? 1 : (want > 4 * CRIT_GRID ? 4 * CRIT_GRID : want));
-  hipLaunchKernelGGL(criteria_grad_kernel, dim3(grid), dim3(256), 0, st, a, b, n, coef, g);
   return (int)hipGetLastError();
 }
 
@@ -666,3 +662,32 @@ int launch_grad_rows(const GrowParams &p0, int ks, int kw, hipStream_t st) {
 }
 
 }  // namespace ssg
+
+// ---- (D) the entry points: every refusal is decided here, before the launch ----
+using namespace ssg;
+
+extern "C" {
+
+size_t ssg_criteria_scratch_bytes(void) { return sizeof(double) * 2 * CRIT_GRID; }
+
+int ssg_criteria_sums(const float *pred, const float *target, size_t n, void *scratch, float *sums_out,
+                      ssg_stream_t stream) {
+  hipStream_t st = (hipStream_t)stream;
+  if (!sums_out || !scratch) return SSG_E_BADARG;
+  if (n == 0) return (int)hipMemsetAsync(sums_out, 0, 2 * sizeof(float), st);
+  if (!pred || !target) return SSG_E_BADARG;
+  return criteria_sums(pred, target, n, scratch, sums_out, st);
+}
+
+int ssg_criteria_grad(const float *pred, const float *target, size_t n, const float *coef, float *grad_pred,
+                      ssg_stream_t stream) {
+  if (n == 0) return 0;
+  if (!pred || !target || !coef || !grad_pred) return SSG_E_BADARG;
+  const size_t want = (n / 4 + 255) / 256;
+  const unsigned grid = (unsigned)(want < 1 ? 1 : (want > 4 * CRIT_GRID ? 4 * CRIT_GRID : want));
+  hipLaunchKernelGGL(criteria_grad_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, pred, target, n, coef,
+                     grad_pred);
+  return (int)hipGetLastError();
+}
+
+}  // extern "C"

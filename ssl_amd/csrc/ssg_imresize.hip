@@ -227,7 +227,7 @@ inline int choose_tile(Args &a, double s, size_t *lds_bytes) {
 
 }  // namespace imresize
 
-int imresize_out_size(int n, double scale) {
+static int imresize_out_size(int n, double scale) {
   if (n < 1 || !imresize::scale_ok(scale)) return SSG_E_BADARG;
   const double m = ceil((double)n * scale);
   if (m < 1.0) return SSG_E_BADARG;
@@ -235,7 +235,7 @@ int imresize_out_size(int n, double scale) {
   return (int)m;
 }
 
-int imresize_taps(double scale, int antialias) {
+static int imresize_taps(double scale, int antialias) {
   if (!imresize::scale_ok(scale)) return SSG_E_BADARG;
   const double kw = (scale < 1.0 && antialias) ? 4.0 / scale : 4.0;
   const double t = ceil(kw);
@@ -255,7 +255,7 @@ static int imresize_axis(int n, int m, double scale, int antialias, double *kw_o
   return 0;
 }
 
-int imresize_table(int n, int m, double scale, int antialias, int *first, double *weights) {
+static int imresize_table(int n, int m, double scale, int antialias, int *first, double *weights) {
   using namespace imresize;
   if (!first || !weights) return SSG_E_BADARG;
   double kw = 0.0;
@@ -277,7 +277,7 @@ int imresize_table(int n, int m, double scale, int antialias, int *first, double
   return 0;
 }
 
-int imresize_tiles(double scale, int antialias, int *tiles, int capacity, int *chosen) {
+static int imresize_tiles(double scale, int antialias, int *tiles, int capacity, int *chosen) {
   using namespace imresize;
   if (capacity < 0 || (capacity > 0 && !tiles)) return SSG_E_BADARG;
   for (int t = 0; t < N_TILES && t < capacity; ++t) tiles[2 * t] = TILES[t][0], tiles[2 * t + 1] = TILES[t][1];
@@ -294,9 +294,9 @@ int imresize_tiles(double scale, int antialias, int *tiles, int capacity, int *c
   return N_TILES;
 }
 
-int launch_imresize(const void *src, int in_kind, int B, int C, int Hin, int Win, double scale, int antialias,
-                    const int *yfirst, const double *yweights, const int *xfirst, const double *xweights, int out_kind,
-                    void *out, hipStream_t st) {
+static int launch_imresize(const void *src, int in_kind, int B, int C, int Hin, int Win, double scale, int antialias,
+                           const int *yfirst, const double *yweights, const int *xfirst, const double *xweights, int out_kind,
+                           void *out, hipStream_t st) {
   using namespace imresize;
   if (!src || !out || src == out || !yfirst || !yweights || !xfirst || !xweights) return SSG_E_BADARG;
   if (B < 1 || C < 1 || Hin < 1 || Win < 1) return SSG_E_BADARG;

@@ -389,20 +389,20 @@ inline size_t image_stride(int H, int W) {
 
 }  // namespace jpegcodec
 
-size_t jpeg_roundtrip_workspace_bytes(int B, int H, int W, int channels) {
+static size_t jpeg_roundtrip_workspace_bytes(int B, int H, int W, int channels) {
   using namespace jpegcodec;
   if (B < 1 || H < 1 || W < 1 || (channels != 1 && channels != 3)) return 0;
   return two_launches(channels) ? (size_t)B * image_stride(H, W) : 0;
 }
 
-int jpeg_unit_table(float *table) {
+static int jpeg_unit_table(float *table) {
   if (!table) return SSG_E_BADARG;
   for (int v = 0; v < 256; ++v) table[v] = jpegcodec::unit_value(v);
   return 0;
 }
 
-int launch_jpeg_roundtrip(const void *in, void *out, int B, int H, int W, int channels, const int *qualities,
-                          int in_layout, int out_epilogue, void *workspace, size_t workspace_bytes, hipStream_t st) {
+static int launch_jpeg_roundtrip(const void *in, void *out, int B, int H, int W, int channels, const int *qualities,
+                                 int in_layout, int out_epilogue, void *workspace, size_t workspace_bytes, hipStream_t st) {
   using namespace jpegcodec;
   if (!in || !out || in == out || !qualities) return SSG_E_BADARG;
   if (B < 1 || H < 1 || W < 1 || (channels != 1 && channels != 3)) return SSG_E_BADARG;

@@ -7,12 +7,14 @@
 // Everything is fp64 -- Sigma's inverse, q, pow / exp / j1, the sum and the division; in fp32 the tails and the sum
 // miss the reference's fp32 result by up to 2e4 ulps -- and the store is the only fp32 rounding.  The work is tiny
 // (a batch of 16 samples is 48 workgroups): what a call costs is its one copy and its one launch.
+// This file defines the entry point ssg_synth_kernels, at its end.
 #include "../../include/ssg_hip.h"
 
 #include "ssg_host.hpp"
 
 namespace ssg {
 
+constexpr int SYNTH_MAX_PAD = 21;     // the largest padded kernel (stock Real-ESRGAN's; filter2d's largest k)
 constexpr int KSYN_NT = 256;          // threads per workgroup: >= SYNTH_MAX_PAD^2 / 2
 constexpr int KSYN_MAX_GRID = 1024;   // workgroups per launch; workgroup b makes outputs b, b + grid, ...
 static_assert(2 * KSYN_NT >= SYNTH_MAX_PAD * SYNTH_MAX_PAD, "two elements per thread cover the largest output");
@@ -85,12 +87,29 @@ __global__ __launch_bounds__(KSYN_NT) void synth_kernels(const ssg_kernel_record
   }
 }
 
-int launch_synth_kernels(const ssg_kernel_record *records_dev, int n, int pad_to, float *out, hipStream_t st) {
-  if (n <= 0) return 0;
-  if (pad_to < 1 || pad_to > SYNTH_MAX_PAD || !(pad_to & 1)) return -1;
+}  // namespace ssg
+
+// ---- (I) the entry points: every refusal is decided here, before the launch ----
+using namespace ssg;
+
+extern "C" {
+
+int ssg_synth_kernels(const ssg_kernel_record *records, int n, int pad_to, ssg_kernel_record *records_dev, float *out,
+                      ssg_stream_t stream) {
+  if (n < 0 || pad_to < 1 || pad_to > SYNTH_MAX_PAD || !(pad_to & 1)) return SSG_E_BADARG;
+  if (n == 0) return 0;
+  if (!records || !records_dev || !out) return SSG_E_BADARG;
+  for (int i = 0; i < n; ++i) {
+    const ssg_kernel_record &r = records[i];
+    if (r.kind < SSG_KERNEL_PULSE || r.kind > SSG_KERNEL_PLATEAU) return SSG_E_BADARG;
+    if (r.size < 1 || !(r.size & 1) || r.size > pad_to) return SSG_E_BADARG;
+  }
+  const int rc = (int)hipMemcpyAsync(records_dev, records, (size_t)n * sizeof(ssg_kernel_record), hipMemcpyHostToDevice,
+                                     (hipStream_t)stream);
+  if (rc) return rc;
   const unsigned grid = (unsigned)(n < KSYN_MAX_GRID ? n : KSYN_MAX_GRID);
-  hipLaunchKernelGGL(synth_kernels, dim3(grid), dim3(KSYN_NT), 0, st, records_dev, n, pad_to, out);
+  hipLaunchKernelGGL(synth_kernels, dim3(grid), dim3(KSYN_NT), 0, (hipStream_t)stream, records_dev, n, pad_to, out);
   return (int)hipGetLastError();
 }
 
-}  // namespace ssg
+}  // extern "C"

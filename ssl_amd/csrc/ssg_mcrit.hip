@@ -180,8 +180,6 @@ inline int for_each_launch(size_t K, const size_t *x, const size_t *g, const siz
   return 0;
 }
 
-inline bool unaligned(size_t p, size_t a) { return p % a != 0; }
-
 // what the two entry points check of the pairs; `grad` may be null (the sums call) and may hold null addresses
 static int check_pairs(size_t K, const size_t *x, const size_t *g, const size_t *grad, const size_t *counts,
                        const double *w, int kind, float eps, size_t *total) {
@@ -200,12 +198,12 @@ static int check_pairs(size_t K, const size_t *x, const size_t *g, const size_t 
 
 }  // namespace mcrit
 
-int mcrit_chunk() { return mcrit::tuning.chunk; }
+static int mcrit_chunk() { return mcrit::tuning.chunk; }
 
-int mcrit_grid_cap() { return mcrit::tuning.grid_cap; }
+static int mcrit_grid_cap() { return mcrit::tuning.grid_cap; }
 
-int launch_mcrit_sums(size_t K, const size_t *x, const size_t *g, const size_t *counts, const double *w, int kind,
-                      float eps, void *workspace, double *sums_out, hipStream_t st) {
+static int launch_mcrit_sums(size_t K, const size_t *x, const size_t *g, const size_t *counts, const double *w, int kind,
+                             float eps, void *workspace, double *sums_out, hipStream_t st) {
   using namespace mcrit;
   return for_each_launch(
       K, x, g, nullptr, counts, w, [](size_t) { return true; },
@@ -221,8 +219,9 @@ int launch_mcrit_sums(size_t K, const size_t *x, const size_t *g, const size_t *
       });
 }
 
-int launch_mcrit_grad(size_t K, const size_t *x, const size_t *g, const size_t *grad, const size_t *counts,
-                      const double *w, int kind, float eps, const double *sums, const double *coef, hipStream_t st) {
+static int launch_mcrit_grad(size_t K, const size_t *x, const size_t *g, const size_t *grad, const size_t *counts,
+                             const double *w, int kind, float eps, const double *sums, const double *coef,
+                             hipStream_t st) {
   using namespace mcrit;
   return for_each_launch(
       K, x, g, grad, counts, w, [&](size_t k) { return grad[k] != 0; },
@@ -260,7 +259,7 @@ int ssg_mcrit_sums(size_t n_tensors, const size_t *x, const size_t *g, const siz
   const int rc = mcrit::check_pairs(n_tensors, x, g, nullptr, counts, weights, kind, eps, &total);
   if (rc && rc != SSG_E_ALIGN) return rc;
   if (workspace_bytes < sizeof(double) * total) return SSG_E_WORKSPACE;
-  if (rc || mcrit::unaligned((size_t)workspace, 8) || mcrit::unaligned((size_t)sums_out, 8)) return SSG_E_ALIGN;
+  if (rc || unaligned(workspace, 8) || unaligned(sums_out, 8)) return SSG_E_ALIGN;
   return launch_mcrit_sums(n_tensors, x, g, counts, weights, kind, eps, workspace, sums_out, (hipStream_t)stream);
 }
 
@@ -270,7 +269,7 @@ int ssg_mcrit_grad(size_t n_tensors, const size_t *x, const size_t *g, const siz
   size_t total = 0;
   if (!grad || !sums || !coef) return SSG_E_BADARG;
   if (const int rc = mcrit::check_pairs(n_tensors, x, g, grad, counts, weights, kind, eps, &total)) return rc;
-  if (mcrit::unaligned((size_t)sums, 8) || mcrit::unaligned((size_t)coef, 8)) return SSG_E_ALIGN;
+  if (unaligned(sums, 8) || unaligned(coef, 8)) return SSG_E_ALIGN;
   return launch_mcrit_grad(n_tensors, x, g, grad, counts, weights, kind, eps, sums, coef, (hipStream_t)stream);
 }
 

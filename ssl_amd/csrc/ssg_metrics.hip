@@ -248,7 +248,7 @@ inline Layout layout(const Args &a) {
 
 }  // namespace metric
 
-size_t metric_workspace_bytes(int B, int C, int H, int W, int crop) {
+static size_t metric_workspace_bytes(int B, int C, int H, int W, int crop) {
   using namespace metric;
   if (check_shape(SSG_METRIC_F32_RGB, B, C, H, W, crop, K)) return 0;
   Args a{};

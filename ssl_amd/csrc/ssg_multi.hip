@@ -19,7 +19,7 @@
 // always accessed 16 bytes wide between its head and tail; src is read 16 bytes wide where it shares dst's alignment
 // and element by element where it does not.  A chunk word that points outside the table's own tensors or past a
 // tensor's end is skipped.  No LDS, no atomics, no scratch.
-// The launcher trusts its arguments: ssg_multi_apply below refuses bad ones before the launch.
+// This file defines the entry points ssg_multi_* at its end; ssg_multi_apply refuses bad arguments before the launch.
 #include "ssg_chunked.hpp"
 
 namespace ssg {
@@ -83,22 +83,6 @@ static size_t table_words(size_t n_tensors, size_t n_chunks) { return HEADER_WOR
 
 }  // namespace multi
 
-int multi_chunk() { return multi::tuning.chunk; }
-
-int multi_grid_cap() { return multi::tuning.grid_cap; }
-
-int launch_multi_apply(const void *table, size_t n_chunks, int kind, float d, float a, const float *w, hipStream_t st) {
-  using namespace multi;
-  const auto go = [&](auto k) {
-    hipLaunchKernelGGL(multi_kernel<decltype(k)::value>, dim3(grid_of(n_chunks, tuning)), dim3(NT), 0, st,
-                       (const word *)table, d, a, w);
-  };
-  if (kind == SSG_MT_EMA) go(std::integral_constant<int, SSG_MT_EMA>{});
-  else if (kind == SSG_MT_LIT) go(std::integral_constant<int, SSG_MT_LIT>{});
-  else go(std::integral_constant<int, SSG_MT_COPY>{});
-  return (int)hipGetLastError();
-}
-
 }  // namespace ssg
 
 // ---- (S) the entry points: every refusal is decided here, before the launch ----
@@ -106,20 +90,20 @@ using namespace ssg;
 
 extern "C" {
 
-int ssg_multi_chunk(void) { return multi_chunk(); }
+int ssg_multi_chunk(void) { return multi::tuning.chunk; }
 
-int ssg_multi_grid_cap(void) { return multi_grid_cap(); }
+int ssg_multi_grid_cap(void) { return multi::tuning.grid_cap; }
 
 size_t ssg_multi_chunks(size_t n_tensors, const size_t *counts) {
   size_t total = 0;
   if (n_tensors && !counts) return 0;
-  return multi::count_chunks(n_tensors, counts, (size_t)multi_chunk(), &total) ? total : (size_t)INT_MAX + 1;
+  return multi::count_chunks(n_tensors, counts, (size_t)ssg_multi_chunk(), &total) ? total : (size_t)INT_MAX + 1;
 }
 
 size_t ssg_multi_table_bytes(size_t n_tensors, const size_t *counts) {
   size_t total = 0;
   if ((n_tensors && !counts) || n_tensors > (size_t)INT_MAX) return 0;
-  if (!multi::count_chunks(n_tensors, counts, (size_t)multi_chunk(), &total)) return 0;
+  if (!multi::count_chunks(n_tensors, counts, (size_t)ssg_multi_chunk(), &total)) return 0;
   return sizeof(multi::word) * multi::table_words(n_tensors, total);
 }
 
@@ -127,15 +111,15 @@ int ssg_multi_table_fill(size_t n_tensors, const size_t *dst, const size_t *src,
                          size_t table_bytes) {
   using namespace multi;
   if (!table || (n_tensors && (!dst || !src || !counts))) return SSG_E_BADARG;
-  if ((size_t)table % sizeof(word)) return SSG_E_ALIGN;
+  if (unaligned(table, sizeof(word))) return SSG_E_ALIGN;
   if (n_tensors > (size_t)INT_MAX) return SSG_E_TOOLARGE;
-  const size_t chunk = (size_t)multi_chunk();
+  const size_t chunk = (size_t)ssg_multi_chunk();
   size_t total = 0;
   if (!count_chunks(n_tensors, counts, chunk, &total)) return SSG_E_TOOLARGE;
   for (size_t i = 0; i < n_tensors; ++i) {
     if (counts[i] == 0) continue;                     // (an empty tensor's pointers are never used)
     if (!dst[i] || !src[i]) return SSG_E_BADARG;
-    if (dst[i] % sizeof(float) || src[i] % sizeof(float)) return SSG_E_ALIGN;
+    if (unaligned(dst[i], sizeof(float)) || unaligned(src[i], sizeof(float))) return SSG_E_ALIGN;
   }
   if (table_bytes < sizeof(word) * table_words(n_tensors, total)) return SSG_E_WORKSPACE;
   word *out = (word *)table;
@@ -152,10 +136,18 @@ int ssg_multi_apply(const void *table, size_t n_chunks, int kind, float d, float
                     ssg_stream_t stream) {
   if (!table || kind < SSG_MT_EMA || kind > SSG_MT_COPY || d != d || a != a) return SSG_E_BADARG;
   if (kind == SSG_MT_LIT && !w_dev) return SSG_E_BADARG;
-  if ((size_t)table % sizeof(multi::word) || (size_t)w_dev % sizeof(float)) return SSG_E_ALIGN;
+  if (unaligned(table, sizeof(multi::word)) || unaligned(w_dev, sizeof(float))) return SSG_E_ALIGN;
   if (n_chunks > (size_t)INT_MAX) return SSG_E_TOOLARGE;
   if (n_chunks == 0) return 0;                          // a set of empty tensors: nothing to launch
-  return launch_multi_apply(table, n_chunks, kind, d, a, w_dev, (hipStream_t)stream);
+  using namespace multi;
+  const auto go = [&](auto k) {
+    hipLaunchKernelGGL(multi_kernel<decltype(k)::value>, dim3(grid_of(n_chunks, tuning)), dim3(NT), 0, (hipStream_t)stream,
+                       (const word *)table, d, a, w_dev);
+  };
+  if (kind == SSG_MT_EMA) go(std::integral_constant<int, SSG_MT_EMA>{});
+  else if (kind == SSG_MT_LIT) go(std::integral_constant<int, SSG_MT_LIT>{});
+  else go(std::integral_constant<int, SSG_MT_COPY>{});
+  return (int)hipGetLastError();
 }
 
 #ifdef SSG_PROFILE

@@ -80,7 +80,7 @@ __device__ __forceinline__ float plane_value(const void *img, const Args &a, int
 // partials in it are read as 16-byte pairs)
 inline int check_workspace(const void *ws, size_t ws_bytes, size_t needed) {
   if (ws_bytes < needed) return SSG_E_WORKSPACE;
-  if ((uintptr_t)ws & 15) return SSG_E_ALIGN;
+  if (unaligned(ws, 16)) return SSG_E_ALIGN;
   return 0;
 }
 

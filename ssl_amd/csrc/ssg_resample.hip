@@ -264,11 +264,11 @@ inline bool choose_tile(Args &a, int filter, size_t *lds_bytes) {
 
 }  // namespace resample
 
-int resample_max_ratio() { return resample::MAX_RATIO; }
+static int resample_max_ratio() { return resample::MAX_RATIO; }
 
-void resample_tile_shape(int *th, int *tw) { *th = resample::TILES[0][0], *tw = resample::TILES[0][1]; }
+static void resample_tile_shape(int *th, int *tw) { *th = resample::TILES[0][0], *tw = resample::TILES[0][1]; }
 
-int resample_ksize(int in, int out, int filter) {
+static int resample_ksize(int in, int out, int filter) {
   if (in < 1 || out < 1 || !resample::filter_ok(filter)) return SSG_E_BADARG;
   double fs = (double)in / out;
   if (fs < 1.0) fs = 1.0;
@@ -277,7 +277,7 @@ int resample_ksize(int in, int out, int filter) {
   return (int)c * 2 + 1;
 }
 
-int resample_table(int in, int out, int filter, int *bounds, int *coef) {
+static int resample_table(int in, int out, int filter, int *bounds, int *coef) {
   using namespace resample;
   if (!bounds || !coef) return SSG_E_BADARG;
   const int ksize = resample_ksize(in, out, filter);
@@ -306,9 +306,9 @@ int resample_table(int in, int out, int filter, int *bounds, int *coef) {
   return 0;
 }
 
-int launch_resample(const uint8_t *src, int B, int C, int Hin, int Win, int Hout, int Wout, int filter,
-                    const int *xbounds, const int *xcoef, const int *ybounds, const int *ycoef, int out_kind, void *out,
-                    hipStream_t st) {
+static int launch_resample(const uint8_t *src, int B, int C, int Hin, int Win, int Hout, int Wout, int filter,
+                           const int *xbounds, const int *xcoef, const int *ybounds, const int *ycoef, int out_kind, void *out,
+                           hipStream_t st) {
   using namespace resample;
   if (!src || !out || (const void *)src == out) return SSG_E_BADARG;
   if (B < 1 || (C != 1 && C != 3) || Hin < 1 || Win < 1 || Hout < 1 || Wout < 1 || !filter_ok(filter)) return SSG_E_BADARG;

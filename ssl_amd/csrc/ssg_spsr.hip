@@ -24,7 +24,8 @@
 // the rows above and below in one load each where W is a multiple of 4 and the group lies in one row; the gather
 // kernels read their distance-2 neighbourhood element by element from L1 / L2 (lanes are consecutive: coalesced).
 // A plane's results do not depend on the planes around it: plane p of a batch is the same bits as the plane alone.
-// The launchers trust their arguments: the entry points in ssg_api.hip refuse bad ones before any launch.
+// This file defines the entry points ssg_spsr_* (eight) and ssg_pixel_sums / ssg_pixel_grad, at its end: they refuse bad
+// arguments before any launch.
 #include "ssg_stream.hpp"
 
 namespace ssg {
@@ -243,22 +244,20 @@ __global__ __launch_bounds__(NT) void pixel_grad_kernel(const float *a, const fl
 
 inline Planes planes_of(int planes, int H, int W) { return Planes{(unsigned)H, (unsigned)W, (size_t)planes * H * W}; }
 
-}  // namespace spsr
-
-int spsr_grid_cap() { return spsr::MAX_WG; }
-
-size_t spsr_workspace_bytes() { return sizeof(double) * spsr::MAX_WG; }
-
-int launch_spsr_map(const float *x, int planes, int H, int W, float *map, hipStream_t st) {
-  using namespace spsr;
-  const Planes g = planes_of(planes, H, W);
-  hipLaunchKernelGGL(spsr_map_kernel, dim3(grid_for(g.n, EPT)), dim3(NT), 0, st, x, g, map);
-  return (int)hipGetLastError();
+static int check_planes(int planes, int H, int W) {
+  if (planes < 1 || H < 1 || W < 1) return SSG_E_BADARG;
+  return (unsigned long long)planes * (unsigned long long)H * (unsigned long long)W >= (1ull << 31) ? SSG_E_BADARG : 0;
 }
 
-int launch_spsr_loss(const float *x, const float *t, int planes, int H, int W, int kind, float eps, float *map_out,
-                     void *workspace, double *sum_out, hipStream_t st) {
-  using namespace spsr;
+static int check_kind(int kind, float eps) {
+  if (kind < SSG_PIX_L1 || kind > SSG_PIX_CHARBONNIER) return SSG_E_BADARG;
+  return eps >= 0.f && eps <= 3.402823466e38f ? 0 : SSG_E_BADARG;   // (a NaN fails both comparisons)
+}
+
+// (file-local and in front of launch_gather, which has two callers: the order in which this file first names its kernel
+// templates is the order of the kernels in the code object)
+static int launch_loss(const float *x, const float *t, int planes, int H, int W, int kind, float eps, float *map_out,
+                       void *workspace, double *sum_out, hipStream_t st) {
   const Planes g = planes_of(planes, H, W);
   const unsigned grid = grid_for(g.n, EPT);
   double *part = partials_of(grid, workspace, sum_out);
@@ -268,9 +267,9 @@ int launch_spsr_loss(const float *x, const float *t, int planes, int H, int W, i
   return finish_sums<1>(grid, part, sum_out, st);
 }
 
-int launch_spsr_gather(const float *x, const float *t, const float *gmap, const double *coef, int planes, int H, int W,
-                       int kind, float eps, float *dx, hipStream_t st) {
-  using namespace spsr;
+// t == nullptr: the map's own adjoint of gmap; else the fused loss's, coef[0] crit' (+ gmap where given)
+static int launch_gather(const float *x, const float *t, const float *gmap, const double *coef, int planes, int H, int W,
+                         int kind, float eps, float *dx, hipStream_t st) {
   const Planes g = planes_of(planes, H, W);
   const unsigned grid = grid_for(g.n, 1);
   if (!t) {
@@ -284,9 +283,67 @@ int launch_spsr_gather(const float *x, const float *t, const float *gmap, const 
   return (int)hipGetLastError();
 }
 
-int launch_spsr_branch_sums(const float *branch, const float *gt, int planes, int H, int W, int kind, float eps,
-                            void *workspace, double *sum_out, hipStream_t st) {
-  using namespace spsr;
+}  // namespace spsr
+
+}  // namespace ssg
+
+// ---- (R) the entry points: every refusal is decided here, before the launch ----
+using namespace ssg;
+using namespace ssg::spsr;
+
+extern "C" {
+
+size_t ssg_spsr_workspace_bytes(void) { return sizeof(double) * MAX_WG; }
+
+int ssg_spsr_grid_cap(void) { return MAX_WG; }
+
+int ssg_spsr_map(const float *x, int planes, int H, int W, float *map, ssg_stream_t stream) {
+  if (!x || !map) return SSG_E_BADARG;
+  if (const int rc = check_planes(planes, H, W)) return rc;
+  if (unaligned(x, 4) || unaligned(map, 4)) return SSG_E_ALIGN;
+  const Planes g = planes_of(planes, H, W);
+  hipLaunchKernelGGL(spsr_map_kernel, dim3(grid_for(g.n, EPT)), dim3(NT), 0, (hipStream_t)stream, x, g, map);
+  return (int)hipGetLastError();
+}
+
+int ssg_spsr_map_backward(const float *x, const float *grad_map, int planes, int H, int W, float *grad_x,
+                          ssg_stream_t stream) {
+  if (!x || !grad_map || !grad_x) return SSG_E_BADARG;
+  if (const int rc = check_planes(planes, H, W)) return rc;
+  if (unaligned(x, 4) || unaligned(grad_map, 4) || unaligned(grad_x, 4)) return SSG_E_ALIGN;
+  return launch_gather(x, nullptr, grad_map, nullptr, planes, H, W, SSG_PIX_L1, 0.f, grad_x, (hipStream_t)stream);
+}
+
+int ssg_spsr_loss(const float *x, const float *target, int planes, int H, int W, int kind, float eps, float *map_out,
+                  void *workspace, double *sum_out, ssg_stream_t stream) {
+  if (!x || !target || !workspace || !sum_out) return SSG_E_BADARG;
+  if (const int rc = check_planes(planes, H, W)) return rc;
+  if (const int rc = check_kind(kind, eps)) return rc;
+  if (unaligned(x, 4) || unaligned(target, 4) || unaligned(map_out, 4) || unaligned(workspace, 8) ||
+      unaligned(sum_out, 8))
+    return SSG_E_ALIGN;
+  return launch_loss(x, target, planes, H, W, kind, eps, map_out, workspace, sum_out, (hipStream_t)stream);
+}
+
+int ssg_spsr_loss_backward(const float *x, const float *target, const float *grad_map, const double *coef, int planes,
+                           int H, int W, int kind, float eps, float *grad_x, ssg_stream_t stream) {
+  if (!x || !target || !coef || !grad_x) return SSG_E_BADARG;
+  if (const int rc = check_planes(planes, H, W)) return rc;
+  if (const int rc = check_kind(kind, eps)) return rc;
+  if (unaligned(x, 4) || unaligned(target, 4) || unaligned(grad_map, 4) || unaligned(grad_x, 4) ||
+      unaligned(coef, 8))
+    return SSG_E_ALIGN;
+  return launch_gather(x, target, grad_map, coef, planes, H, W, kind, eps, grad_x, (hipStream_t)stream);
+}
+
+int ssg_spsr_branch_loss(const float *branch, const float *gt, int planes, int H, int W, int kind, float eps,
+                         void *workspace, double *sum_out, ssg_stream_t stream) {
+  if (!branch || !gt || !workspace || !sum_out) return SSG_E_BADARG;
+  if (const int rc = check_planes(planes, H, W)) return rc;
+  if (const int rc = check_kind(kind, eps)) return rc;
+  if (unaligned(branch, 4) || unaligned(gt, 4) || unaligned(workspace, 8) || unaligned(sum_out, 8))
+    return SSG_E_ALIGN;
+  hipStream_t st = (hipStream_t)stream;
   const Planes g = planes_of(planes, H, W);
   const unsigned grid = grid_for(g.n, EPT);
   double *part = partials_of(grid, workspace, sum_out);
@@ -296,36 +353,47 @@ int launch_spsr_branch_sums(const float *branch, const float *gt, int planes, in
   return finish_sums<1>(grid, part, sum_out, st);
 }
 
-int launch_spsr_branch_grad(const float *branch, const float *gt, int planes, int H, int W, int kind, float eps,
-                            const double *coef, float *grad, hipStream_t st) {
-  using namespace spsr;
+int ssg_spsr_branch_grad(const float *branch, const float *gt, int planes, int H, int W, int kind, float eps,
+                         const double *coef, float *grad_branch, ssg_stream_t stream) {
+  if (!branch || !gt || !coef || !grad_branch) return SSG_E_BADARG;
+  if (const int rc = check_planes(planes, H, W)) return rc;
+  if (const int rc = check_kind(kind, eps)) return rc;
+  if (unaligned(branch, 4) || unaligned(gt, 4) || unaligned(grad_branch, 4) || unaligned(coef, 8))
+    return SSG_E_ALIGN;
   const Planes g = planes_of(planes, H, W);
   with_pixel_kind(kind, [&](auto k) {
-    hipLaunchKernelGGL(spsr_branch_grad_kernel<decltype(k)::value>, dim3(grid_for(g.n, EPT)), dim3(NT), 0, st, branch, gt,
-                       g, eps, coef, grad);
+    hipLaunchKernelGGL(spsr_branch_grad_kernel<decltype(k)::value>, dim3(grid_for(g.n, EPT)), dim3(NT), 0,
+                       (hipStream_t)stream, branch, gt, g, eps, coef, grad_branch);
   });
   return (int)hipGetLastError();
 }
 
-int launch_pixel_sums(const float *a, const float *b, size_t n, int kind, float eps, void *workspace, double *sum_out,
-                      hipStream_t st) {
-  using namespace spsr;
+int ssg_pixel_sums(const float *pred, const float *target, size_t n, int kind, float eps, void *workspace,
+                   double *sum_out, ssg_stream_t stream) {
+  if (!pred || !target || !workspace || !sum_out || n < 1) return SSG_E_BADARG;
+  if (const int rc = check_kind(kind, eps)) return rc;
+  if (unaligned(pred, 4) || unaligned(target, 4) || unaligned(workspace, 8) || unaligned(sum_out, 8))
+    return SSG_E_ALIGN;
+  hipStream_t st = (hipStream_t)stream;
   const unsigned grid = grid_for(n, EPT);
   double *part = partials_of(grid, workspace, sum_out);
   with_pixel_kind(kind, [&](auto k) {
-    hipLaunchKernelGGL(pixel_sums_kernel<decltype(k)::value>, dim3(grid), dim3(NT), 0, st, a, b, n, eps, part);
+    hipLaunchKernelGGL(pixel_sums_kernel<decltype(k)::value>, dim3(grid), dim3(NT), 0, st, pred, target, n, eps, part);
   });
   return finish_sums<1>(grid, part, sum_out, st);
 }
 
-int launch_pixel_grad(const float *a, const float *b, size_t n, int kind, float eps, const double *coef, float *grad,
-                      hipStream_t st) {
-  using namespace spsr;
+int ssg_pixel_grad(const float *pred, const float *target, size_t n, int kind, float eps, const double *coef,
+                   float *grad_pred, ssg_stream_t stream) {
+  if (!pred || !target || !coef || !grad_pred || n < 1) return SSG_E_BADARG;
+  if (const int rc = check_kind(kind, eps)) return rc;
+  if (unaligned(pred, 4) || unaligned(target, 4) || unaligned(grad_pred, 4) || unaligned(coef, 8))
+    return SSG_E_ALIGN;
   with_pixel_kind(kind, [&](auto k) {
-    hipLaunchKernelGGL(pixel_grad_kernel<decltype(k)::value>, dim3(grid_for(n, EPT)), dim3(NT), 0, st, a, b, n, eps, coef,
-                       grad);
+    hipLaunchKernelGGL(pixel_grad_kernel<decltype(k)::value>, dim3(grid_for(n, EPT)), dim3(NT), 0, (hipStream_t)stream,
+                       pred, target, n, eps, coef, grad_pred);
   });
   return (int)hipGetLastError();
 }
 
-}  // namespace ssg
+}  // extern "C"

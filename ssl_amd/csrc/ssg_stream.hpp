@@ -167,8 +167,9 @@ inline unsigned grid_for(size_t n, int per_thread) {
 inline double *partials_of(unsigned grid, void *workspace, double *out) { return grid == 1 ? out : (double *)workspace; }
 
 // the partials' fold behind a sums kernel (a single workgroup has written `out` itself)
+// (static: where a caller does not inline it, the library's dynamic symbols still stay as they were)
 template <int NV, class Out>
-inline int finish_sums(unsigned grid, const double *part, Out *out, hipStream_t st) {
+static inline int finish_sums(unsigned grid, const double *part, Out *out, hipStream_t st) {
   if (grid > 1) hipLaunchKernelGGL((fold_kernel<NV, Out>), dim3(1), dim3(NT), 0, st, part, (int)grid, out);
   return (int)hipGetLastError();
 }

@@ -1,7 +1,10 @@
 """The reference side of tests/test_gpu_datapath.py, pinned on the CPU where no fixture reaches: the numpy oracle
 (oracle/datapath_oracle.py) against torch's own CPU evaluation of the same calls at the sweep's shapes, and the
-properties of the sweep's inputs (tests/datapath_cases.py) that the GPU comparisons take for granted.  CPU only.
+properties of the sweep's inputs (tests/datapath_cases.py) that the GPU comparisons take for granted; and the refusals
+of the data path's C-ABI entry points, which are decided before anything is launched.  CPU only.
 """
+import ctypes
+
 import numpy as np
 import pytest
 import torch
@@ -193,3 +196,121 @@ def test_noise_oracles_equal_torch_fp32_bit_for_bit(clip, rounds):
     nz = (nz * (1 - gg) + ng * gg) * _t(scale).view(8, 1, 1, 1)
     ref = _torch_clip_round(tx + nz, clip, rounds)
     assert np.array_equal(dp.poisson_noise(x, scale, g8, dcol, dgray, clip, rounds), ref.numpy())
+
+
+# ---- the C ABI's refusals, in the order include/ssg_hip.h documents them: decided before any launch ----
+def _fake(k):
+    return ctypes.c_void_p(k << 20)       # never dereferenced: every call below returns before anything reads it
+
+
+def test_c_abi_augment_crop_and_pool_swap_refuse_before_any_launch():
+    from ssl_amd import _lib
+    L = _lib.lib()
+    BAD = -1
+    src, dst, par = _fake(1), _fake(2), _fake(3)
+    ok = dict(src=src, dst=dst, eb=4, B=2, C=3, Hs=9, Ws=8, Ho=5, Wo=4, par=par)
+
+    def crop(**kw):
+        a = dict(ok, **kw)
+        return L.ssg_augment_crop(a["src"], a["dst"], a["eb"], a["B"], a["C"], a["Hs"], a["Ws"], a["Ho"], a["Wo"], a["par"], None)
+
+    for name in ("src", "dst", "par"):
+        assert crop(**{name: None}) == BAD
+    assert crop(B=-1) == BAD
+    for name in ("C", "Hs", "Ws", "Ho", "Wo"):
+        for v in (0, -3):
+            assert crop(**{name: v}) == BAD
+    for eb in (2, 0, 3, 8, -4):
+        assert crop(eb=eb) == BAD
+    assert crop(B=0) == 0                                   # nothing to move: no launch
+    assert crop(B=0, eb=2) == BAD and crop(B=0, src=None) == BAD   # ... but the arguments are checked first
+
+    q, b, s = _fake(4), _fake(5), _fake(6)
+    assert L.ssg_pool_swap(None, b, 48, s, 2, None) == BAD
+    assert L.ssg_pool_swap(q, None, 48, s, 2, None) == BAD
+    assert L.ssg_pool_swap(q, b, 48, None, 2, None) == BAD
+    assert L.ssg_pool_swap(q, b, 48, s, -1, None) == BAD
+    assert L.ssg_pool_swap(q, b, 48, s, 0, None) == 0 and L.ssg_pool_swap(q, b, 0, s, 2, None) == 0   # nothing to move
+    assert L.ssg_pool_swap(None, b, 0, s, 0, None) == BAD   # checked first
+
+
+def test_c_abi_usm_sharp_refuses_before_any_launch():
+    from ssl_amd import _lib
+    L = _lib.lib()
+    BAD, WS, SMALL = -1, -3, -4
+    img, out, scr = _fake(1), _fake(2), _fake(3)
+    ok = dict(img=img, out=out, B=2, C=3, H=40, W=37, radius=50, scr=scr, nb=None)
+
+    def usm(**kw):
+        a = dict(ok, **kw)
+        nb = L.ssg_usm_scratch_bytes(a["B"], a["C"], a["H"], a["W"]) if a["nb"] is None else a["nb"]
+        return L.ssg_usm_sharp(a["img"], a["out"], a["B"], a["C"], a["H"], a["W"], a["radius"], 0.0, 0.5, 10.0, a["scr"], nb, None)
+
+    assert L.ssg_usm_scratch_bytes(2, 3, 40, 37) == 3 * 4 * 2 * 3 * 40 * 37
+    # every call is refused by exactly what it names: the rest of `ok` would be served (H, W = 40, 37 > 51 / 2)
+    assert usm(B=-1) == BAD and usm(radius=-1) == BAD
+    for name in ("C", "H", "W"):
+        for v in (0, -2):
+            assert usm(**{name: v}) == BAD
+    assert usm(B=0) == 0
+    assert usm(B=0, img=None, out=None, scr=None, nb=0) == 0        # B == 0 is answered before the pointers are looked at
+    assert usm(B=0, C=0) == BAD and usm(B=0, radius=-1) == BAD      # ... and after the sizes
+    for name in ("img", "out", "scr"):
+        assert usm(**{name: None}) == BAD
+    assert usm(out=img) == BAD                                     # img == out
+    full = L.ssg_usm_scratch_bytes(2, 3, 40, 37)
+    assert usm(nb=full - 1) == WS and usm(nb=0) == WS
+    assert usm(scr=None, nb=0) == BAD and usm(out=img, nb=0) == BAD  # pointers before the scratch size
+    for radius in (64, 65, 1000):                                   # kernel sizes 65, 65, 1001: more than 63 taps
+        assert usm(radius=radius) == BAD
+        assert usm(radius=radius, nb=full - 1) == WS                # the scratch size before the kernel size
+        assert usm(radius=radius, H=3) == BAD                       # the kernel size before the image size
+    for radius, side in ((50, 25), (51, 25), (63, 31), (62, 31), (3, 1), (2, 1)):   # kernel size radius | 1; H, W <= R
+        assert usm(radius=radius, H=side) == SMALL and usm(radius=radius, W=side) == SMALL
+        assert usm(radius=radius, H=side, nb=12 * 2 * 3 * side * 37 - 1) == WS      # the scratch size before the image size
+    assert usm(H=1, W=1) == SMALL
+
+
+def test_c_abi_filter2d_and_diffjpeg_refuse_before_any_launch():
+    from ssl_amd import _lib
+    L = _lib.lib()
+    BAD, SMALL = -1, -4
+    img, ker, out = _fake(1), _fake(2), _fake(3)
+    ok = dict(img=img, ker=ker, out=out, B=2, C=3, H=17, W=30, k=7, nk=2)
+
+    def filt(**kw):
+        a = dict(ok, **kw)
+        return L.ssg_filter2d(a["img"], a["ker"], a["out"], a["B"], a["C"], a["H"], a["W"], a["k"], a["nk"], None)
+
+    assert filt(B=-1) == BAD
+    for name in ("C", "H", "W"):
+        for v in (0, -2):
+            assert filt(**{name: v}) == BAD
+    assert filt(B=0) == 0
+    assert filt(B=0, img=None, ker=None, out=None, k=4, nk=7) == 0   # B == 0 is answered before anything else but the sizes
+    assert filt(B=0, W=0) == BAD
+    for name in ("img", "ker", "out"):
+        assert filt(**{name: None}) == BAD
+    assert filt(out=img) == BAD
+    for k in (0, -1, 2, 4, 20, 22, 23, 51):                          # even, non-positive, more than 21
+        assert filt(k=k) == BAD
+        assert filt(k=k, H=1, W=1) == BAD                            # the kernel size before the image size
+    for nk in (0, 3, -1):                                            # neither 1 nor B
+        assert filt(nk=nk) == BAD
+        assert filt(nk=nk, k=21, H=10) == BAD                        # ... before the image size too
+    for k, side in ((7, 3), (21, 10), (3, 1), (9, 4)):
+        assert filt(k=k, H=side) == SMALL and filt(k=k, W=side) == SMALL and filt(k=k, H=side, nk=1) == SMALL
+        assert filt(k=k, H=side, img=None) == BAD and filt(k=k, H=side, out=img) == BAD   # the pointers before the image size
+
+    def jpeg(img=img, out=out, B=2, H=17, W=30, qdev=None, q=50.0):
+        return L.ssg_diffjpeg(img, out, B, H, W, qdev, q, None)
+
+    assert jpeg(B=-1) == BAD
+    for v in (0, -2):
+        assert jpeg(H=v) == BAD and jpeg(W=v) == BAD
+    assert jpeg(B=0) == 0 and jpeg(B=0, img=None, out=None, q=0.0) == 0
+    assert jpeg(B=0, H=0) == BAD
+    assert jpeg(img=None) == BAD and jpeg(out=None) == BAD
+    for q in (0.0, -5.0, float("nan"), -float("inf")):               # no device qualities and no positive host quality
+        assert jpeg(q=q) == BAD
+    assert jpeg(img=None, qdev=ker, q=0.0) == BAD

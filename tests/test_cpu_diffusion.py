@@ -360,12 +360,14 @@ def test_exports_declarations_and_bindings(L):
         header = f.read()
     with open(os.path.join(ROOT, "ssl_amd", "csrc", "ssg_host.hpp")) as f:
         host = f.read()
+    with open(os.path.join(ROOT, "ssl_amd", "csrc", "ssg_diffusion.hip")) as f:
+        beside = f.read()
     for name in NAMES:
         assert name in _lib.PROTOTYPES and getattr(L, name).argtypes == _lib.PROTOTYPES[name][1], name
         assert re.search(r"\b%s\(" % name, header), name
-    for name in ("launch_diff_combine", "launch_diff_p_sample", "launch_diff_loss_sums", "launch_diff_loss_finish",
-                 "launch_diff_loss_grad", "launch_diff_canvas_gather", "launch_diff_canvas_stitch"):
-        assert name in host, name
+        # every entry point is defined beside its kernels; nothing of the family crosses the host seam
+        assert len(re.findall(r"^[a-z_ ]+\b%s\(" % name, beside, flags=re.M)) == 1, name
+    assert "diff" not in host
     assert "ssg_diff_combine" in re.findall(r"/\* 6, additive:.*?\*/", header, flags=re.S)[-1]
     assert L.ssg_abi_version() == 6
     assert (diffusion.EPS, diffusion.X0, diffusion.V) == (0, 1, 2)
@@ -455,6 +457,25 @@ def test_every_refusal_is_decided_before_a_launch(L):
     assert stitch(n_preds=0) == stitch(ntiles=0) == stitch(ts=9) == stitch(B=0) == E["BADARG"]
     assert stitch(n_preds=2 ** 24) == stitch(h=2 ** 16, w=2 ** 16) == E["TOOLARGE"]
     assert stitch(preds=p + 2) == stitch(tiles=p + 2) == stitch(out=p + 2) == stitch(wts=p + 4) == E["ALIGN"]
+    # two things wrong at once: null pointers and bad scalars, then the shape (bad, then too large), then the workspace's
+    # size, then every alignment
+    huge = dict(B=2 ** 20, n=chunk << 12)
+    assert combine(x=None, **huge) == combine(clamp=1, lo=1.0, hi=-1.0, **huge) == combine(T=0, **huge) == E["BADARG"]
+    assert combine(x=p + 2, **huge) == E["TOOLARGE"] and combine(x=p + 2, T=0) == E["BADARG"]
+    assert p_sample(param=3, **huge) == p_sample(ra=None, **huge) == p_sample(T=0, **huge) == E["BADARG"]
+    assert p_sample(x=p + 1, **huge) == E["TOOLARGE"] and p_sample(t=p + 4, n=0) == E["BADARG"]
+    assert sums(kind=2, **huge) == sums(ws=None, **huge) == E["BADARG"]
+    assert sums(nbytes=0, **huge) == sums(pred=p + 2, **huge) == E["TOOLARGE"]
+    assert sums(nbytes=15, pred=p + 2) == sums(nbytes=15, ws=p + 4) == E["WORKSPACE"] and sums(nbytes=0, B=0) == E["BADARG"]
+    assert finish(lsw=nan, **huge) == finish(S=None, **huge) == finish(nbytes=0, T=0) == E["BADARG"]
+    assert finish(nbytes=0, **huge) == finish(B=2 ** 31, n=1, nbytes=0) == finish(B=2 ** 31, n=1, ws=p + 4) == E["TOOLARGE"]
+    assert finish(nbytes=8, ws=p + 4) == finish(nbytes=8, lv=p + 2) == E["WORKSPACE"]
+    assert grad(kind=2, **huge) == grad(gx0=p, t=None, **huge) == grad(pred=p + 2, n=0) == E["BADARG"]
+    assert grad(pred=p + 2, **huge) == grad(coef=p + 4, **huge) == E["TOOLARGE"]
+    assert gather(src=None, h=2 ** 16, w=2 ** 16) == gather(ntiles=0, h=2 ** 16, w=2 ** 16) == gather(src=p + 2, ts=9) == E["BADARG"]
+    assert gather(src=p + 2, h=2 ** 16, w=2 ** 16) == E["TOOLARGE"]
+    assert stitch(bstep=2, n_preds=2 ** 24) == stitch(n_preds=0, h=2 ** 16, w=2 ** 16) == stitch(out=p + 2, B=0) == E["BADARG"]
+    assert stitch(preds=p + 2, n_preds=2 ** 24) == stitch(wts=p + 4, h=2 ** 16, w=2 ** 16) == E["TOOLARGE"]
     assert np.array_equal(buf, before)
 
 

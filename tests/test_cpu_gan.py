@@ -250,3 +250,12 @@ def test_c_abi_refuses_before_any_launch():
     assert grad_call(coef=None) == BAD and grad_call(grad=None) == BAD
     assert sums_call(x=ctypes.c_void_p((1 << 20) + 2)) == -5 and grad_call(grad=ctypes.c_void_p((3 << 20) + 2)) == -5
     assert sums_call(sums=ctypes.c_void_p((4 << 20) + 4)) == -5 and grad_call(coef=ctypes.c_void_p((5 << 20) + 4)) == -5
+    # two things wrong at once: the logits (null, n, kind, sign, then their alignment) are judged before the other
+    # pointers, and a null pointer before any of those is measured
+    odd, half = ctypes.c_void_p((1 << 20) + 2), ctypes.c_void_p((4 << 20) + 4)
+    for call in (sums_call, grad_call):
+        assert call(x=odd, kind=5) == BAD and call(x=odd, n=0) == BAD and call(x=odd, sign=0.0) == BAD
+    assert sums_call(x=odd, work=None) == -5 and sums_call(x=odd, sums=None) == -5
+    assert grad_call(x=odd, coef=None) == -5 and grad_call(x=odd, grad=None) == -5
+    assert sums_call(work=None, sums=half) == BAD and sums_call(work=half, sums=None) == BAD
+    assert grad_call(coef=None, grad=odd) == BAD and grad_call(coef=half, grad=None) == BAD

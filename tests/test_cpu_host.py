@@ -357,6 +357,28 @@ def test_argument_checks_need_no_gpu():
     assert L.ssg_backward_scratch_bytes(100, 25) >= 100 * 625 * 4
 
 
+def test_criteria_on_foreign_tensors_refuse_before_any_launch():
+    """ssg_criteria_sums / ssg_criteria_grad: the outputs are looked at first, then n == 0, then the inputs.  (The
+    n == 0 call of ssg_criteria_sums clears sums_out on the device and is not made here.)"""
+    from ssl_amd import _lib
+    L = _lib.lib()
+    pred, target, scratch, sums, coef, grad = (ctypes.c_void_p(k << 20) for k in range(1, 7))   # never dereferenced
+    for n in (1, 70, 1 << 33):
+        assert L.ssg_criteria_sums(pred, target, n, scratch, None, None) == -1
+        assert L.ssg_criteria_sums(pred, target, n, None, sums, None) == -1
+        assert L.ssg_criteria_sums(None, target, n, scratch, sums, None) == -1
+        assert L.ssg_criteria_sums(pred, None, n, scratch, sums, None) == -1
+        assert L.ssg_criteria_grad(None, target, n, coef, grad, None) == -1
+        assert L.ssg_criteria_grad(pred, None, n, coef, grad, None) == -1
+        assert L.ssg_criteria_grad(pred, target, n, None, grad, None) == -1
+        assert L.ssg_criteria_grad(pred, target, n, coef, None, None) == -1
+    # the outputs come before n == 0 for the sums; n == 0 comes before every pointer for the gradient
+    assert L.ssg_criteria_sums(None, None, 0, scratch, None, None) == -1
+    assert L.ssg_criteria_sums(None, None, 0, None, sums, None) == -1
+    assert L.ssg_criteria_grad(None, None, 0, None, None, None) == 0
+    assert L.ssg_criteria_grad(pred, target, 0, coef, grad, None) == 0
+
+
 def test_criteria_trip_sizes_cross_the_grid_caps():
     """The sizes of test_gpu_ref_api's trip tests against the criteria grid read off the scratch size (two fp64 per
     workgroup of the sums; the gradient runs four times as many): more 256-lane float4 workgroups than the grid has, by

@@ -262,3 +262,13 @@ def test_c_abi_refuses_before_any_launch():
     assert plane_calls(("loss", "branch_loss"), w=half) == {ALIGN}
     assert plane_calls(("loss_backward", "branch_grad"), k=half) == {ALIGN}
     assert L.ssg_spsr_loss(a, b, 6, 9, 11, 1, 0.0, c, work, half, None) == ALIGN
+    # two things wrong at once: null pointers, then the shape, then kind and eps, then every alignment
+    for bad in (dict(planes=0), dict(W=-3), dict(planes=1 << 11, H=1 << 10, W=1 << 10)):
+        assert plane_calls(ALL, p=odd, **bad) == {BAD}, bad
+        assert plane_calls(("loss", "branch_loss"), w=half, **bad) == {BAD}, bad
+    for bad in (dict(kind=3), dict(eps=float("nan"))):
+        assert plane_calls(WITH_KIND, p=odd, **bad) == {BAD}, bad
+        assert flat_calls(q=odd, **bad) == {BAD}, bad
+    assert plane_calls(ALL, p=odd, r=None) == {BAD} and plane_calls(ALL, p=None, r=odd) == {BAD}
+    assert flat_calls(p=odd, n=0) == {BAD} and flat_calls(p=odd, r=None) == {BAD}
+    assert plane_calls(("loss_backward", "branch_grad"), p=odd, k=None) == {BAD}

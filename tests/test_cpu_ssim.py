@@ -222,6 +222,14 @@ def test_c_abi_refuses_before_any_launch():
     assert call(FAKE, FAKE2, ok, 11, FAKE3, FAKE4, FAKE5, nb - 1) == WS
     assert call(FAKE, FAKE2, ok, 11, None, FAKE4, FAKE5, nb - 1) == WS         # the loss-only entry too
     assert call(FAKE, FAKE2, ok, 11, FAKE3, FAKE4, ctypes.c_void_p((5 << 20) + 8), nb) == ALIGN
+    # two things wrong at once: the pointers, then the shape, then the window, then the workspace's size, then its alignment
+    big, odd = (4, 3, 16384, 16384), ctypes.c_void_p((5 << 20) + 8)
+    assert call(None, FAKE2, big, 11, FAKE3, FAKE4, FAKE5, 1 << 30) == BAD
+    assert call(FAKE, FAKE2, big, 11, FAKE, FAKE4, FAKE5, 1 << 30) == BAD
+    assert call(FAKE, FAKE2, big, 4, FAKE3, FAKE4, FAKE5, 0) == BIG
+    assert call(FAKE, FAKE2, (0, 3, 40, 37), 4, FAKE3, FAKE4, odd, 0) == BAD
+    assert call(FAKE, FAKE2, ok, 4, FAKE3, FAKE4, odd, nb - 1) == BAD
+    assert call(FAKE, FAKE2, ok, 11, FAKE3, FAKE4, odd, nb - 1) == WS
 
 
 def test_python_argument_errors_without_a_device():
