@@ -1,6 +1,7 @@
-"""How every call of the C ABI reaches the GPU: the device that holds the call's tensors is made current, the handle of
-torch's current stream on it is the entry point's last argument, and the status is checked.  The one spelling of that
-for the whole package, and of the few helpers that go with it; it imports torch and ._lib only.
+"""Whether a call goes to the C ABI at all -- the switch of set_native_criteria and `native`: fp32 tensors on one GPU --
+and how it reaches the GPU: the device that holds the call's tensors is made current, the handle of torch's current
+stream on it is the entry point's last argument, and the status is checked.  The one spelling of both for the whole
+package, and of the few helpers that go with them; it imports torch and ._lib only.
 """
 import contextlib
 
@@ -12,6 +13,41 @@ from . import _lib
 # call is what is left to save); torch.cuda.current_stream() where this torch has no such function
 _RAW_STREAM = getattr(torch._C, "_cuda_getCurrentRawStream", None)
 _NOTHING = contextlib.nullcontext()
+
+
+_NATIVE_CRITERIA = True
+
+
+def set_native_criteria(on):
+    """The switch behind ssl_amd.losses.set_native_criteria; returns the previous setting."""
+    global _NATIVE_CRITERIA
+    prev, _NATIVE_CRITERIA = _NATIVE_CRITERIA, bool(on)
+    return prev
+
+
+def native_criteria():
+    return _NATIVE_CRITERIA
+
+
+def readable(*tensors):
+    """Whether the kernels can be handed these tensors' addresses at all: fp32 tensors on one GPU.  Whatever the switch
+    says: a tensor of another type or device must never reach the C ABI."""
+    dev = None
+    for t in tensors:       # (one plain loop: this runs on every call of every criterion)
+        if not (isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32):
+            return False
+        if dev is None:
+            dev = t.device
+        elif t.device != dev:
+            return False
+    return dev is not None
+
+
+def native(*tensors):
+    """Whether a module's call takes the kernels, as far as every family agrees: the switch is on and the kernels can
+    read the tensors.  Each family adds its own conditions ("Which calls take the kernels").  The switch is
+    tested first: a deferred handle (losses/lazy.py) is refused once per image, by `isinstance`."""
+    return _NATIVE_CRITERIA and readable(*tensors)
 
 
 def ptr(t):

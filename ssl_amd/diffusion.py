@@ -14,9 +14,10 @@
                              weighted stitch in one launch
     ImageSpliterTh           scripts/util_image.py:686-769; gather() is the same stitch with unit weights
 
-The native domain: fp32 contiguous GPU tensors on one device, no input that requires a gradient (the criterion excepted:
-it is the differentiable piece), `ssl_amd.losses.set_native_criteria(True)`.  Anything else -- CPU tensors, fp64, half,
-bf16, an input in a graph -- takes the reference's torch lines and gives their bits.
+The native domain ("Which calls take the kernels"): fp32 contiguous GPU tensors on one device, no input that
+requires a gradient (the criterion excepted: it is the differentiable piece),
+`ssl_amd.losses.set_native_criteria(True)`.  Anything else -- CPU tensors, fp64, half, bf16, an input in a graph -- takes
+the reference's torch lines and gives their bits.
 
 `t` is an int64 tensor on the tensors' device and is never read on the host: the coefficients are gathered by the kernels.
 The contract for its values is 0 <= t < T; a GPU sample whose t is outside gets NaN results (nothing is read outside a
@@ -27,7 +28,6 @@ import numpy as np
 import torch
 
 from . import _gpu, _lib
-from .losses import basic_loss
 
 __all__ = ["Schedule", "make_beta_schedule", "space_timesteps", "p_losses_criterion", "canvas_tiles", "gaussian_weights",
            "canvas_gather", "canvas_stitch", "p_sample_canvas_step", "ImageSpliterTh", "loss_sums"]
@@ -197,7 +197,7 @@ class Schedule:
         _check_t(t, self.num_timesteps, x.shape[0])
         _table_on(self.sigma, x)
         B, n = _rows(x, model_out, noise)
-        if not _native(t, x, model_out, noise):
+        if not _native((x, model_out, noise), t):
             return _p_sample_torch(self, x, model_out, t, noise, clip_denoised, return_x0)
         x, model_out, noise, t = x.contiguous(), model_out.contiguous(), noise.contiguous(), t.contiguous()
         out = torch.empty_like(x)
@@ -215,14 +215,13 @@ def extract_into_tensor(a, t, x_shape):
     return a.gather(-1, t).reshape(t.shape[0], *((1,) * (len(x_shape) - 1)))
 
 
-def _native(t, *tensors):
-    """Whether the kernels take the call: the package's rule (fp32 tensors and an int64 t on one GPU, the switch on), and
-    nothing in an autograd graph."""
-    first = tensors[0]
-    if not (basic_loss._NATIVE_CRITERIA and first.is_cuda and t.device == first.device and t.dtype == torch.int64):
+def _native(tensors, t=None, no_grad=None):
+    """Whether the kernels take the call: the package's rule (_gpu.native: the switch, fp32 tensors on one GPU), `t`, where
+    the call has one, an int64 tensor on that GPU, and nothing in an autograd graph -- none of `no_grad` (None: of the
+    tensors) requires grad while grad is enabled."""
+    if not _gpu.native(*tensors) or (t is not None and (t.device != tensors[0].device or t.dtype != torch.int64)):
         return False
-    return all(x.device == first.device and x.dtype == torch.float32
-               and not (x.requires_grad and torch.is_grad_enabled()) for x in tensors)
+    return not (torch.is_grad_enabled() and any(x.requires_grad for x in (tensors if no_grad is None else no_grad)))
 
 
 def _rows(*tensors):
@@ -256,7 +255,7 @@ def _combine(A, x, Bt, y, t, subtract, clamp=None):
     _check_t(t, A.shape[0], x.shape[0])
     _table_on(A, x)
     B, n = _rows(x, y)
-    if not _native(t, x, y):
+    if not _native((x, y), t):
         a, b = extract_into_tensor(A, t, x.shape) * x, extract_into_tensor(Bt, t, x.shape) * y
         out = a - b if subtract else a + b
         return out if clamp is None else out.clamp_(*clamp)
@@ -409,10 +408,8 @@ def p_losses_criterion(model_output, target, x_noisy, t, schedule, logvar, loss_
         raise ValueError("ssl_amd.diffusion: the criterion takes tensors of (B, ...) with at least two dimensions")
     if logvar.shape != (schedule.num_timesteps,):
         raise ValueError(f"ssl_amd.diffusion: logvar must have shape ({schedule.num_timesteps},), got {tuple(logvar.shape)}")
-    native = (basic_loss._NATIVE_CRITERIA and all(x.is_cuda and x.dtype == torch.float32 and x.device == t.device
-                                                   for x in (model_output, target, x_noisy, logvar)) and t.is_cuda
-              and not ((target.requires_grad or x_noisy.requires_grad) and torch.is_grad_enabled()))
-    if native:
+    # (the differentiable piece: model_output and logvar may require grad, target and x_noisy may not)
+    if _native((model_output, target, x_noisy, logvar), t, no_grad=(target, x_noisy)):
         loss, x0, logged = _Criterion.apply(model_output, logvar, target, x_noisy, t, schedule, _KIND[loss_type],
                                             float(l_simple_weight), float(original_elbo_weight), learn)
     else:
@@ -484,11 +481,6 @@ def _tile_table(records, dev):
     return _TABLES[key]
 
 
-def _canvas_native(*tensors):
-    return basic_loss._NATIVE_CRITERIA and all(x.is_cuda and x.dtype == torch.float32 and x.device == tensors[0].device
-                                               and not (x.requires_grad and torch.is_grad_enabled()) for x in tensors)
-
-
 def canvas_gather(x, tiles, tile_size):
     """Every tile of x (B, C, h, w) in one launch: (len(tiles) B, C, ts, ts), tile k's samples at [k B, (k + 1) B) -- the
     order in which the reference concatenates its `input_list`."""
@@ -499,7 +491,7 @@ def canvas_gather(x, tiles, tile_size):
     for oy, ox in tiles:
         if oy < 0 or ox < 0 or oy + ts > h or ox + ts > w:
             raise ValueError(f"ssl_amd.diffusion: tile at ({oy}, {ox}) of size {ts} leaves the {h} x {w} canvas")
-    if not _canvas_native(x):
+    if not _native((x,)):
         return torch.cat([x[:, :, oy:oy + ts, ox:ox + ts] for oy, ox in tiles], dim=0)
     x = x.contiguous()
     with _gpu.on(x.device):
@@ -540,7 +532,7 @@ def canvas_stitch(preds, tiles, shape, tile_weights=None, grid=None, per_sample=
         if tile_weights.dtype != torch.float64:
             raise TypeError("ssl_amd.diffusion: tile_weights must be float64 (gaussian_weights), as the reference's are")
         w4 = tile_weights.expand(B, C, ts, ts)
-    if not _canvas_native(preds) or (w4 is not None and w4.device != preds.device):
+    if not _native((preds,)) or (w4 is not None and w4.device != preds.device):
         out = torch.zeros(shape, device=preds.device, dtype=preds.dtype)
         cnt = torch.zeros(shape, device=preds.device, dtype=preds.dtype)
         for oy, ox, src in records:
@@ -632,7 +624,7 @@ class ImageSpliterTh:
         ph, pw = self._patches[0].shape[-2:]
         square = all(p.shape[-2:] == (ph, ph) for p in self._patches)
         first = self._patches[0]
-        if not (square and _canvas_native(*self._patches) and first.dtype == self.im_ori.dtype):
+        if not (square and _native(self._patches) and first.dtype == self.im_ori.dtype):
             res = torch.zeros(self._shape, dtype=self.im_ori.dtype, device=self.im_ori.device)
             cnt = torch.zeros(self._shape, dtype=self.im_ori.dtype, device=self.im_ori.device)
             for p, (y, x) in zip(self._patches, self._at):

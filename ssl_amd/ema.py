@@ -36,7 +36,6 @@ from torch.nn.parallel import DataParallel, DistributedDataParallel
 from . import _gpu, _lib
 from ._gpu import address_array
 from ._gpu import dense_strides as _dense
-from .losses import basic_loss
 
 __all__ = ["ModelEma", "model_ema", "update_E", "LitEma", "get_bare_model"]
 
@@ -164,8 +163,8 @@ class _Updater:
 
     def run(self, dst, src, kind, decay=0.0, w=None):
         sig = self.signature(dst + src)
-        if sig != self._sig or self._flag != basic_loss._NATIVE_CRITERIA:
-            self._flag = basic_loss._NATIVE_CRITERIA
+        if sig != self._sig or self._flag != _gpu.native_criteria():
+            self._flag = _gpu.native_criteria()
             self._build(dst, src)
             self._sig = sig
         if self._tables:

@@ -12,7 +12,7 @@ import torch
 from . import _lib
 # the launch helpers under the names this module (and its tests and tools) has always used for them
 from ._gpu import address_array, dense_strides, launch as _launch, need_gpu as _need_gpu, ptr as _ptr  # noqa: F401
-from ._gpu import stream as _stream, workspace as _workspace  # noqa: F401
+from ._gpu import readable as _readable, stream as _stream, workspace as _workspace  # noqa: F401
 
 
 def _f32c(t):
@@ -833,13 +833,13 @@ def check_ssim_window(window_size):
 PIXEL_KINDS = {name: _lib.CONSTANTS["SSG_PIX_" + name.upper()] for name in ("l1", "mse", "charbonnier")}
 
 
-def _pixel_kind(kind, eps):
-    if kind not in PIXEL_KINDS:
-        raise ValueError(f"ssl_amd: criterion must be one of {sorted(PIXEL_KINDS)}, got {kind!r}")
+def _pixel_kind(kind, eps, kinds=PIXEL_KINDS):
+    if kind not in kinds:
+        raise ValueError(f"ssl_amd: criterion must be one of {sorted(kinds)}, got {kind!r}")
     eps = float(eps)
     if not 0.0 <= eps < float("inf"):
         raise ValueError(f"ssl_amd: eps must be finite and not negative, got {eps!r}")
-    return PIXEL_KINDS[kind], eps
+    return kinds[kind], eps
 
 
 def _planes(name, x, *same):
@@ -1007,12 +1007,10 @@ MULTI_KINDS = dict(PIXEL_KINDS, fro=_lib.CONSTANTS["SSG_PIX_FRO"])
 
 
 def multi_pair_is_native(pred, target):
-    """Whether the pair can go to the kernels as it lies in memory: fp32 tensors of one non-empty shape on one GPU with
-    equal dense strides (dense_strides)."""
-    return (isinstance(pred, torch.Tensor) and isinstance(target, torch.Tensor) and pred.is_cuda
-            and pred.device == target.device and pred.dtype == torch.float32 and target.dtype == torch.float32
-            and pred.shape == target.shape and pred.numel() > 0 and pred.stride() == target.stride()
-            and dense_strides(pred))
+    """Whether the pair can go to the kernels as it lies in memory: fp32 tensors on one GPU (_gpu.readable: whatever the
+    switch says, which governs the modules) of one non-empty shape with equal dense strides (dense_strides)."""
+    return (_readable(pred, target) and pred.shape == target.shape and pred.numel() > 0
+            and pred.stride() == target.stride() and dense_strides(pred))
 
 
 class _MultiPixelFn(torch.autograd.Function):
@@ -1058,11 +1056,7 @@ def multi_pixel_loss(preds, targets, weights, kind='l1', eps=1e-12, reduction='m
     of each difference (the reduction is not read).  Every pair must satisfy multi_pair_is_native; the gradient goes
     to each pred that requires it, and targets must not require grad.  return_sums=True returns (loss, the K + 1
     device doubles S_0 .. S_{K-1}, total)."""
-    if kind not in MULTI_KINDS:
-        raise ValueError(f"ssl_amd: criterion must be one of {sorted(MULTI_KINDS)}, got {kind!r}")
-    eps = float(eps)
-    if not 0.0 <= eps < float("inf"):
-        raise ValueError(f"ssl_amd: eps must be finite and not negative, got {eps!r}")
+    code, eps = _pixel_kind(kind, eps, MULTI_KINDS)
     preds, targets, weights = list(preds), list(targets), [float(v) for v in weights]
     K = len(preds)
     if K < 1 or len(targets) != K or len(weights) != K:
@@ -1081,5 +1075,5 @@ def multi_pixel_loss(preds, targets, weights, kind='l1', eps=1e-12, reduction='m
     if any(v != v for v in weights):
         raise ValueError("ssl_amd: multi_pixel_loss takes weights that are numbers, got a NaN")
     scaled = [v / p.numel() if mean else v for v, p in zip(weights, preds)]
-    loss, sums = _MultiPixelFn.apply(MULTI_KINDS[kind], eps, scaled, K, *preds, *targets)
+    loss, sums = _MultiPixelFn.apply(code, eps, scaled, K, *preds, *targets)
     return (loss, sums) if return_sums else loss

@@ -23,29 +23,52 @@ from .. import _gpu, _lib, engine
 _reduction_modes = ['none', 'mean', 'sum']
 
 
-_NATIVE_CRITERIA = True
+def _check_reduction(reduction):
+    if reduction not in _reduction_modes:
+        raise ValueError(f'Unsupported reduction mode: {reduction}. Supported ones are: {_reduction_modes}')
 
 
 def set_native_criteria(on):
     """Route L1Loss / KLDistanceLoss on materialised fp32 GPU tensors through the engine's streaming criteria kernels
     (default) or through the reference's torch expressions (needed for a second derivative through the criterion:
-    the native autograd node is once-differentiable).  Returns the previous setting."""
-    global _NATIVE_CRITERIA
-    prev, _NATIVE_CRITERIA = _NATIVE_CRITERIA, bool(on)
-    return prev
+    the native autograd node is once-differentiable), and every other family of the package with them (DESIGN.md,
+    "Which calls take the kernels").  Returns the previous setting."""
+    return _gpu.set_native_criteria(on)
 
 
 def _native_pair(pred, target):
-    """Whether (pred, target) can go through the engine's streaming criteria kernels (ssg_criteria_sums / _grad): real
-    fp32 tensors of one shape on ONE GPU, no gradient wanted for the target.  (The native node is once-differentiable:
-    a caller that needs a second derivative through the criterion -- gradient penalties -- passes tensors under
-    `torch.autograd.graph`'s usual rules and gets an error from autograd, not a wrong value; `set_native_criteria(False)`
-    restores the reference's torch expressions.)  Deferred handles (losses/lazy.py) are not
-    tensors: they take the torch calls below, which is where they are intercepted."""
-    return (_NATIVE_CRITERIA and isinstance(pred, torch.Tensor) and isinstance(target, torch.Tensor)
-            and pred.is_cuda and target.is_cuda and pred.device == target.device
-            and pred.dtype == torch.float32 and target.dtype == torch.float32 and pred.shape == target.shape
+    """Whether (pred, target) can go through the engine's streaming criteria kernels (ssg_criteria_sums / _grad): the
+    package's rule (_gpu.native: the switch, fp32 tensors on ONE GPU), one non-empty shape, no gradient wanted for the
+    target.  (The native node is once-differentiable: a caller that needs a second derivative through the criterion --
+    gradient penalties -- passes tensors under `torch.autograd.graph`'s usual rules and gets an error from autograd,
+    not a wrong value; `set_native_criteria(False)` restores the reference's torch expressions.)  Deferred handles
+    (losses/lazy.py) are not tensors: they take the torch calls below, which is where they are intercepted.  The
+    reference's loop hands them over once per image, so a handle is turned away here, before the rule is called: the
+    `isinstance` decides nothing that the rule does not decide again."""
+    return (isinstance(pred, torch.Tensor) and _gpu.native(pred, target) and pred.shape == target.shape
             and pred.numel() > 0 and not target.requires_grad)
+
+
+def weight_reduce_loss(kind, pred, target, weight, eps, loss_weight, reduction):
+    """loss_weight * weighted_loss(criterion)(pred, target, weight, reduction) (loss_util.py:33-62) in torch operations:
+    the element-wise criterion 'l1' | 'mse' | 'charbonnier' (with its eps), the optional weight and the reduction."""
+    if kind == 'l1':
+        loss = F.l1_loss(pred, target, reduction='none')
+    elif kind == 'mse':
+        loss = F.mse_loss(pred, target, reduction='none')
+    else:
+        loss = torch.sqrt((pred - target) ** 2 + eps)
+    if weight is not None:
+        loss = loss * weight
+    if reduction == 'sum':
+        loss = loss.sum()
+    elif reduction == 'mean':
+        if weight is None:
+            loss = loss.mean()
+        else:  # weight_reduce_loss: mean over the weighted region
+            w = weight.sum() if weight.size(1) > 1 else weight.sum() * loss.size(1)
+            loss = loss.sum() / w
+    return loss_weight * loss
 
 
 class _CriterionSum(torch.autograd.Function):
@@ -82,8 +105,7 @@ class L1Loss(nn.Module):
 
     def __init__(self, loss_weight=1.0, reduction='mean'):
         super(L1Loss, self).__init__()
-        if reduction not in _reduction_modes:
-            raise ValueError(f'Unsupported reduction mode: {reduction}. Supported ones are: {_reduction_modes}')
+        _check_reduction(reduction)
         self.loss_weight = loss_weight
         self.reduction = reduction
 
@@ -91,18 +113,7 @@ class L1Loss(nn.Module):
         if weight is None and self.reduction in ('mean', 'sum') and _native_pair(pred, target):
             total = _CriterionSum.apply(pred, target, 0)
             return self.loss_weight * (total / pred.numel() if self.reduction == 'mean' else total)
-        loss = F.l1_loss(pred, target, reduction='none')
-        if weight is not None:
-            loss = loss * weight
-        if self.reduction == 'sum':
-            loss = loss.sum()
-        elif self.reduction == 'mean':
-            if weight is None:
-                loss = loss.mean()
-            else:  # weight_reduce_loss: mean over the weighted region
-                w = weight.sum() if weight.size(1) > 1 else weight.sum() * loss.size(1)
-                loss = loss.sum() / w
-        return self.loss_weight * loss
+        return weight_reduce_loss('l1', pred, target, weight, 0.0, self.loss_weight, self.reduction)
 
 
 class KLDistanceLoss(nn.Module):
@@ -294,8 +305,7 @@ class ArtifactLoss(nn.Module):
 
     def __init__(self, loss_weight=1.0, ksize=7, reduction='mean'):
         super(ArtifactLoss, self).__init__()
-        if reduction not in _reduction_modes:
-            raise ValueError(f'Unsupported reduction mode: {reduction}. Supported ones are: {_reduction_modes}')
+        _check_reduction(reduction)
         self.loss_weight = loss_weight
         self.ksize = ksize
         self.reduction = reduction

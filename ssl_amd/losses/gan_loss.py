@@ -22,7 +22,6 @@ from torch import nn
 from torch.autograd.function import once_differentiable
 
 from .. import _gpu, _lib
-from . import basic_loss
 
 __all__ = ["GANLoss", "MultiScaleGANLoss"]
 
@@ -34,11 +33,14 @@ _FAMILIES = {"vanilla": "bce", "lsgan": "ls", "wgan": "wgan", "wgan_softplus": "
 
 
 def _native(*tensors):
-    """Whether the tensors can go through ssg_gan_sums / ssg_gan_grad: fp32, non-empty, on ONE GPU, the native criteria
-    not switched off (basic_loss.set_native_criteria)."""
-    return (basic_loss._NATIVE_CRITERIA
-            and all(isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.float32 and t.numel() > 0
-                    and t.device == tensors[0].device for t in tensors))
+    """Whether the tensors can go through ssg_gan_sums / ssg_gan_grad: the package's rule (_gpu.native: the switch, fp32
+    tensors on ONE GPU) and none of them empty."""
+    if not _gpu.native(*tensors):
+        return False
+    for t in tensors:       # (a plain loop: a call is host-bound, and a generator costs as much as the rule itself)
+        if t.numel() == 0:
+            return False
+    return True
 
 
 _CONSTANTS, _WORKSPACES = {}, {}

@@ -26,8 +26,7 @@ import torch
 import torch.nn.functional as F
 from torch import nn
 
-from .. import engine
-from . import basic_loss
+from .. import _gpu, engine
 
 __all__ = ["VGGFeatureExtractor", "PerceptualLoss", "vgg_layer_names", "multi_criterion", "VGG_PRETRAIN_PATH",
            "VGG_WEIGHTS_ENV"]
@@ -184,7 +183,7 @@ def multi_criterion(preds, targets, weights, kind='l1', scale=1.0):
     engine.multi_pixel_loss call with the weights scale * weights[k] where every pair can take the kernels, the
     reference's loop of torch operations and its closing product (and their bits) otherwise."""
     preds, targets = list(preds), list(targets)
-    if preds and basic_loss._NATIVE_CRITERIA and all(
+    if preds and _gpu.native_criteria() and all(
             engine.multi_pair_is_native(p, t) and not t.requires_grad and p.device == preds[0].device
             for p, t in zip(preds, targets)):
         return engine.multi_pixel_loss(preds, targets, [float(w) * float(scale) for w in weights], kind)

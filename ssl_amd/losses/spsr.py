@@ -7,31 +7,20 @@ channels.  MSELoss / CharbonnierLoss mirror basicsr/losses/basic_loss.py:69-128.
 `cri_pix_gradSR(G(output), G(gt))` (:363) and `cri_pix_gradBranch(branch, G(gt))` (:368) as one fused call each; the
 reference has no name for them.
 
-Dispatch follows basic_loss._native_pair: fp32 tensors of one shape on one GPU, a target that wants no gradient, no
-element-wise weight and a 'mean' or 'sum' reduction take the kernels; everything else -- CPU tensors, other dtypes,
-`weight=`, 'none', a target that requires grad, `set_native_criteria(False)` -- takes the torch expressions below, which
-are the reference's operations and give its bits.
+Dispatch ("Which calls take the kernels"): fp32 tensors of one shape on one GPU, a target that wants no
+gradient, no element-wise weight and a 'mean' or 'sum' reduction take the kernels; everything else -- CPU tensors, other
+dtypes, `weight=`, 'none', a target that requires grad, `set_native_criteria(False)` -- takes the torch expressions
+below, which are the reference's operations and give its bits.
 """
 import torch
 import torch.nn.functional as F
 from torch import nn
 
-from .. import engine
+from .. import _gpu, engine
 from . import basic_loss
+from .basic_loss import _check_reduction, weight_reduce_loss as _torch_criterion
 
 __all__ = ["Get_gradient", "Get_gradient_nopadding", "GradientLoss", "MSELoss", "CharbonnierLoss"]
-
-_reduction_modes = basic_loss._reduction_modes
-
-
-def _check_reduction(reduction):
-    if reduction not in _reduction_modes:
-        raise ValueError(f'Unsupported reduction mode: {reduction}. Supported ones are: {_reduction_modes}')
-
-
-def _native_one(x):
-    return (basic_loss._NATIVE_CRITERIA and isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.float32
-            and x.dim() == 4 and x.numel() > 0)
 
 
 def _torch_map(x):
@@ -47,35 +36,12 @@ def _torch_map(x):
     return torch.cat(planes, dim=1)
 
 
-def _elementwise(kind, pred, target, eps):
-    if kind == 'l1':
-        return F.l1_loss(pred, target, reduction='none')
-    if kind == 'mse':
-        return F.mse_loss(pred, target, reduction='none')
-    return torch.sqrt((pred - target) ** 2 + eps)
-
-
-def _torch_criterion(kind, pred, target, weight, eps, loss_weight, reduction):
-    """loss_weight * weighted_loss(criterion)(pred, target, weight, reduction) (loss_util.py:33-62) in torch operations."""
-    loss = _elementwise(kind, pred, target, eps)
-    if weight is not None:
-        loss = loss * weight
-    if reduction == 'sum':
-        loss = loss.sum()
-    elif reduction == 'mean':
-        if weight is None:
-            loss = loss.mean()
-        else:  # weight_reduce_loss: mean over the weighted region
-            w = weight.sum() if weight.size(1) > 1 else weight.sum() * loss.size(1)
-            loss = loss.sum() / w
-    return loss_weight * loss
-
-
 class Get_gradient(nn.Module):
     """forward(x): the gradient map of a (B,C,H,W) batch (spsrssl_model.py:18-50), any C."""
 
     def forward(self, x):
-        return engine.gradient_map(x) if _native_one(x) else _torch_map(x)
+        native = _gpu.native(x) and x.dim() == 4 and x.numel() > 0
+        return engine.gradient_map(x) if native else _torch_map(x)
 
 
 class Get_gradient_nopadding(Get_gradient):

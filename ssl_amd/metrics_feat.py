@@ -28,8 +28,7 @@ import torch.nn.functional as F
 from torch import nn
 
 from . import _lib
-from ._gpu import address_array, launch as _launch, ptr as _ptr, workspace as _workspace
-from .losses import basic_loss
+from ._gpu import address_array, launch as _launch, native, ptr as _ptr, readable, workspace as _workspace
 from .losses.perceptual import build_vgg_trunk, vgg_layer_names
 
 __all__ = ["LPIPS", "DISTS", "L2pooling", "ScalingLayer", "calculate_lpips", "calculate_dists", "lpips_dists",
@@ -92,24 +91,14 @@ def dists_torch_lines(feats0, feats1, alpha, beta):
     return 1 - (dist1 + dist2).reshape(-1)
 
 
-def kernels_can_read(*tensors):
-    """Whether the kernels can be handed these tensors' addresses at all: fp32 tensors on one GPU.  Whatever
-    set_native_criteria says: a tensor of another type or device must never reach the C ABI."""
-    if not tensors or not all(isinstance(t, torch.Tensor) for t in tensors):
-        return False
-    dev = tensors[0].device
-    return all(t.is_cuda and t.device == dev and t.dtype == torch.float32 for t in tensors)
-
-
 def features_are_native(*tensors):
-    """Whether a module's call takes the kernels: set_native_criteria on, tensors the kernels can read, none requiring
-    grad (no gradient flows through the kernels)."""
-    return (basic_loss._NATIVE_CRITERIA and kernels_can_read(*tensors)
-            and not any(t.requires_grad for t in tensors))
+    """Whether a module's call takes the kernels: the package's rule (_gpu.native: the switch, fp32 tensors on one GPU)
+    and none requiring grad (no gradient flows through the kernels)."""
+    return native(*tensors) and not any(t.requires_grad for t in tensors)
 
 
 def _refuse_unreadable(name, *tensors):
-    if not kernels_can_read(*tensors):
+    if not readable(*tensors):
         seen = sorted({f"{t.dtype} on {t.device}" if isinstance(t, torch.Tensor) else type(t).__name__ for t in tensors})
         raise ValueError(f"ssl_amd: {name} takes fp32 tensors on one GPU (the kernels read their memory as floats), got "
                          f"{', '.join(seen)}; the packages' torch lines ({name.split('_')[0]}_torch_lines) take anything")
