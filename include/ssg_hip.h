@@ -83,6 +83,9 @@ typedef void *ssg_stream_t; /* hipStream_t */
 /* 6, additive: + ssg_diff_combine, ssg_diff_p_sample, ssg_diff_loss_sums, ssg_diff_loss_finish, ssg_diff_loss_grad,
  * ssg_diff_canvas_gather, ssg_diff_canvas_stitch, ssg_diff_workspace_bytes, ssg_diff_chunk, ssg_diff_grid_cap and
  * SSG_DIFF_EPS / _X0 / _V (the Diffusion fork around its network, section (W)). */
+/* 6, additive once more: + ssg_adam_apply, ssg_adam_table_fill, ssg_adam_grads_fill, ssg_adam_table_bytes, the record
+ * ssg_adam_scalars and SSG_ADAM_PLAIN / _L2 / _DECOUPLED (the Adam and AdamW step of a parameter group in one launch,
+ * section (X)). */
 int ssg_abi_version(void);
 const char *ssg_status_string(int status);
 /* Device-side refusals that no return value can carry (everything is asynchronous): waits for `stream`, then returns
@@ -1299,6 +1302,67 @@ int ssg_diff_canvas_gather(const float *src, const int *tiles /* device */, int 
 int ssg_diff_canvas_stitch(const float *preds, int n_preds, int bstep, const int *tiles /* device */, int ntiles,
                            const double *weights /* nullable */, size_t wsb, size_t wsc, int B, int C, int h, int w,
                            int ts, float *out, ssg_stream_t stream);
+
+/* ---------------------------------------------------------------- (X) ----
+ * The Adam / AdamW step of a whole parameter group as ONE launch, whatever the number of tensors (torch.optim.Adam and
+ * AdamW as basicsr/models/base_model.py:103-120 get_optimizer, train_BSGRAN/models/model_ssl.py:229-230 and the
+ * Diffusion fork's configure_optimizers build them), ssl_amd/csrc/ssg_multi.hip.  Tensors are fp32, walked flat over n
+ * elements each; tensor i is (p, g, m, v): parameter, gradient, exp_avg, exp_avg_sq.  Per element, every operation
+ * fp32 and rounded on its own (no fma), `/` and sqrtf correctly rounded:
+ *   g' = g                               SSG_ADAM_PLAIN
+ *   g' = fl(g + fl(wd p))                SSG_ADAM_L2         Adam's weight decay
+ *   p' = fl(p cwd)                       SSG_ADAM_DECOUPLED  AdamW's; p' = p otherwise
+ *   m  <- fl(m + fl(w1 fl(g' - m)))
+ *   v  <- fl(fl(v b2) + fl(w2 fl(g' g')))
+ *   den = fl(fl(sqrtf(v) / s2) + eps)
+ *   p  <- fl(p' - fl(a fl(m / den)))
+ * Nothing is special-cased: NaN and infinite gradients propagate as the formulas say.  This is torch's single-tensor
+ * Adam operation by operation, NOT torch's bits: torch's lerp_ and vectorised multiply-adds round differently in a
+ * share of the elements (tests/adam_reference.py holds both to an fp64 evaluation).
+ * The scalars are formed by the caller in double, by torch's expressions, and cast to float once each: a = lr / (1 -
+ * beta1^t), w1 = 1 - beta1, b2 = beta2, w2 = 1 - beta2, s2 = (1 - beta2^t)^0.5, cwd = 1 - lr wd.  They travel in the
+ * launch's arguments, so a changed lr or t changes no table; and a HIP graph that captured the call would replay step
+ * t's scalars: DO NOT capture it (torch's Adam without `capturable` has the same limit).
+ * The table is section (S)'s with four words per tensor, {n_tensors, n_chunks, chunk, 0}, then (p address, m address,
+ * v address, n) per tensor, then one word per chunk; the g addresses are an array of n_tensors 8-byte words OF THEIR
+ * OWN, `grads`: gradients move between steps under zero_grad(set_to_none=True), and a moved gradient costs a new image
+ * of that array, not of the table.  Both live ON THE DEVICE at the apply; the fills write host images.
+ * The chunk size, the grid cap and the set's chunk count are section (S)'s: ssg_multi_chunk(), ssg_multi_grid_cap(),
+ *   ssg_multi_chunks().
+ * ssg_adam_table_bytes: the table image's size, 32 + 32 n_tensors + 8 chunks; 0 where ssg_adam_table_fill would refuse
+ *   the counts.  The grads image is 8 n_tensors bytes.
+ * ssg_adam_table_fill: writes both images (HOST memory, 8-byte aligned) from host arrays of addresses and counts.
+ * ssg_adam_grads_fill: writes the grads image alone, for new g addresses and the filled HOST table image of the same
+ *   set; the new addresses are checked against the image's p, m and v ranges.  Neither touches a device.
+ * ssg_adam_apply: ONE launch on `stream`: a workgroup of 256 threads takes a chunk, beyond ssg_multi_grid_cap()
+ *   workgroups further chunks grid-stride.  p is accessed 16 bytes wide behind a scalar head and in front of a scalar
+ *   tail; g, m and v 16 bytes wide where all three share p's alignment mod 16 and element by element otherwise (one
+ *   decision per chunk).  Stores stay inside [p, p + n), [m, m + n) and [v, v + n) of every tensor; g is only read.
+ *   No LDS, no atomics, no scratch; no allocation, copy, synchronisation or host read.  n_chunks = 0 launches nothing.
+ * The caller owns what the images point to: every tensor must be alive and unmoved at each apply.
+ * Status, decided before the launch with every tensor and both images untouched: SSG_E_BADARG for a null image or
+ * scalars (or null arrays with n_tensors > 0, or a null address of a non-empty tensor), two of the 4 n_tensors ranges
+ * of the non-empty tensors that overlap, a table image of another tensor count (ssg_adam_grads_fill), an unknown mode;
+ * SSG_E_ALIGN for an address of a non-empty tensor or a scalars address that is not 4-byte aligned, an image that is
+ * not 8-byte aligned; SSG_E_TOOLARGE for a chunk count (of one tensor or of the set) or a tensor count that does not
+ * fit an int; SSG_E_WORKSPACE for a table_bytes below ssg_adam_table_bytes() or a grads_bytes below 8 n_tensors. */
+#define SSG_ADAM_PLAIN 0
+#define SSG_ADAM_L2 1
+#define SSG_ADAM_DECOUPLED 2
+typedef struct ssg_adam_scalars {
+  float a, w1, b2, w2, s2, eps;
+  float wd;  /* SSG_ADAM_L2 only */
+  float cwd; /* SSG_ADAM_DECOUPLED only */
+  int mode;  /* SSG_ADAM_* */
+} ssg_adam_scalars; /* 36 bytes */
+size_t ssg_adam_table_bytes(size_t n_tensors, const size_t *counts);
+int ssg_adam_table_fill(size_t n_tensors, const size_t *p, const size_t *g, const size_t *m, const size_t *v,
+                        const size_t *counts, void *table /* host */, size_t table_bytes, void *grads /* host */,
+                        size_t grads_bytes);
+int ssg_adam_grads_fill(const void *table /* host */, size_t n_tensors, const size_t *g, void *grads /* host */,
+                        size_t grads_bytes);
+int ssg_adam_apply(const void *table /* device */, const void *grads /* device */, size_t n_chunks,
+                   const ssg_adam_scalars *scalars /* host */, ssg_stream_t stream);
 
 #ifdef SSG_PROFILE
 /* PROFILING BUILD ONLY (libssg_hip_prof.so, compiled with -DSSG_PROFILE; the product library libssg_hip.so does not
