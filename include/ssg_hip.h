@@ -80,6 +80,7 @@ typedef void *ssg_stream_t; /* hipStream_t */
  * SSG_PIX_FRO (a pixel criterion over a ragged set of tensor pairs: the perceptual loss, section (U)). */
 /* 6, additive: + ssg_lpips_layers, ssg_dists_score, ssg_lpips_workspace_bytes, ssg_dists_workspace_bytes,
  * ssg_featmetric_grid_cap / _unit / _chunk (the LPIPS and DISTS criteria over their feature pairs, section (V)). */
+/* 6, additive: + ssg_lpips_layers_backward (the LPIPS criterion's gradient with respect to both feature maps, section (V)). */
 /* 6, additive: + ssg_diff_combine, ssg_diff_p_sample, ssg_diff_loss_sums, ssg_diff_loss_finish, ssg_diff_loss_grad,
  * ssg_diff_canvas_gather, ssg_diff_canvas_stitch, ssg_diff_workspace_bytes, ssg_diff_chunk, ssg_diff_grid_cap and
  * SSG_DIFF_EPS / _X0 / _V (the Diffusion fork around its network, section (W)). */
@@ -1200,6 +1201,22 @@ int ssg_mcrit_grad(size_t n_tensors, const size_t *x, const size_t *g, const siz
  *          pixels of one image of one layer (fewer for a layer of fewer pixels: the power of two at or above H W, its
  *          channels split over the rest of the workgroup); at most ssg_featmetric_grid_cap() workgroups, grid-stride
  *          beyond.  Workspace: 8 bytes per unit.
+ *   ssg_lpips_layers_backward   the gradient of sum_n coef[n] out[n][n_layers] with respect to both sets of maps, in ONE
+ *          launch for all layers and both sides and without a workspace: the adjoint of the UNCLAMPED d (the forward's
+ *          clamp of rounding-negative values has no counterpart).  With the forward's five fp64 sums per pixel, n_s =
+ *          sqrt(P_s), i_s = 1 / (n_s + 1e-10) and s = coef[n] / (H W):
+ *            g0_c = s 2 i0 (w_c (f0_c i0 - f1_c i1) - (A i0 - B i1) (i0 / n0) f0_c)
+ *            g1_c = s 2 i1 (w_c (f1_c i1 - f0_c i0) - (Cc i1 - B i0) (i1 / n1) f1_c)
+ *          every product and sum in fp64 from the exact fp32 inputs, one cast to fp32 at the store.  The forward's work
+ *          units; each walks its channels twice (the sums, then the stores).  coef: n_images floats on the device.
+ *          grad0, grad1: HOST arrays of n_layers device addresses of fp32 maps shaped as f0 / f1 (they may not overlap
+ *          the inputs); either WHOLE array may be NULL where that side wants no gradient.  One writer per element, no
+ *          atomics: the same bits from call to call, image n alone or in a batch, whichever other layers are in the
+ *          call.  Identical inputs give exactly +-0 everywhere.  REPRODUCED ON PURPOSE: a pixel whose own vector is all
+ *          zero (n_s = 0) gets NaN on that side's C elements of that pixel (0 * inf, what torch's autograd gives through
+ *          sqrt's backward at 0) while the other side stays finite there.  A NaN input stays inside its own image.
+ *          Status: SSG_E_BADARG also for a NULL coef, both grad arrays NULL, or a null address inside a given grad
+ *          array; SSG_E_ALIGN for coef or a gradient address that is not 4-byte aligned; the rest as ssg_lpips_layers.
  *   ssg_dists_score    per (image, layer, channel) plane the sums of x, y, x^2, y^2, x y over chunks of
  *          ssg_featmetric_chunk() elements of ONE plane (5 doubles per chunk in `workspace`, chunks ordered layer, image,
  *          channel, chunk of the plane), then mx = Sx / HW, vx = Sxx / HW - mx^2, cov = Sxy / HW - mx my, S1 = (2 mx my +
@@ -1220,6 +1237,10 @@ size_t ssg_lpips_workspace_bytes(int n_layers, int n_images, const int *C, const
 int ssg_lpips_layers(int n_layers, int n_images, const size_t *f0, const size_t *f1, const size_t *w, const int *C,
                      const int *H, const int *W, void *workspace, size_t workspace_bytes, double *out /* device */,
                      ssg_stream_t stream);
+int ssg_lpips_layers_backward(int n_layers, int n_images, const size_t *f0, const size_t *f1, const size_t *w, const int *C,
+                              const int *H, const int *W, const float *coef /* device */,
+                              const size_t *grad0 /* nullable */, const size_t *grad1 /* nullable */,
+                              ssg_stream_t stream);
 size_t ssg_dists_workspace_bytes(int n_layers, int n_images, const int *C, const int *H, const int *W);
 int ssg_dists_score(int n_layers, int n_images, const size_t *x, const size_t *y, const int *C, const int *H,
                     const int *W, const float *alpha /* device */, const float *beta /* device */, void *workspace,

@@ -12,6 +12,16 @@
 //            1e-10):  d = ((A i0) i0 - 2 ((B i0) i1)) + (Cc i1) i1, and 0 where that is negative.  Identical inputs give
 //            the three terms t, 2 t, t and so exactly 0; an all-zero vector gives i = 1e10 and zero sums, so the
 //            package's 0 / (0 + eps) = 0.  A NaN passes through (the clamp is a comparison).
+//   ssg_lpips_layers_backward   the adjoint of the UNCLAMPED d with respect to both maps, in ONE launch for all layers
+//            and both sides, with the forward's units.  Pass 1 forms the five sums exactly as above; slice 0 turns them
+//            into the pixel's six scalars (n = sqrt(P), i = 1 / (n + 1e-10), s = coef[n] / HW)
+//              i0, i1, q0 = (A i0 - B i1) (i0 / n0), q1 = (Cc i1 - B i0) (i1 / n1), m0 = (2 s) i0, m1 = (2 s) i1
+//            and hands them to every slice through LDS; pass 2 walks the slice's channels again (the second read is
+//            meant to hit L2) and stores g0_c = m0 (w_c (f0_c i0 - f1_c i1) - q0 f0_c), g1_c = m1 (w_c (f1_c i1 - f0_c i0)
+//            - q1 f1_c), every operation fp64 and one cast at the store, consecutive lanes to consecutive addresses.
+//            Identical inputs: f0 i0 - f1 i1 and A i0 - B i1 are differences of equal numbers, so every element is +-0.
+//            An all-zero vector (n = 0): q = 0 * inf = NaN on THAT side's C elements of the pixel, as torch's lines give
+//            (0 * inf in sqrt's backward); the other side stays finite.  One writer per element, no workspace.
 //            A work unit is px pixels of one image of one layer, px = the power of two at or above min(HW, 256); the 256
 //            threads are px pixel lanes (consecutive addresses along HW: coalesced) times 256 / px channel slices
 //            (slice s takes channels s, s + 256 / px, ...).  At HW >= 256 a thread owns one pixel and walks all C
@@ -55,6 +65,20 @@ struct LpipsSet {
   LpipsLayer l[MAX_LAYERS];
   int K, N;
   unsigned n_units;
+};
+
+struct LpipsGradLayer {
+  const float *f0, *f1, *w;
+  float *g0, *g1;    // either null for the whole set: that side wants no gradient
+  unsigned C, HW;
+  unsigned first, units, px_log2;   // as LpipsLayer's
+};
+
+struct LpipsGradSet {
+  LpipsGradLayer l[MAX_LAYERS];
+  int K, N;
+  unsigned n_units;
+  const float *coef;   // N: the upstream gradient of out[n][K]
 };
 
 struct DistsLayer {
@@ -153,6 +177,79 @@ __global__ __launch_bounds__(NT) void lpips_fold_kernel(const LpipsSet s, const 
     __syncthreads();
   }
   if (t == 0) out[(size_t)n * (s.K + 1) + s.K] = total;
+}
+
+// the adjoint of lpips_kernel's unclamped d: the same units, the same five sums, then a second walk that stores
+__global__ __launch_bounds__(NT) void lpips_grad_kernel(const LpipsGradSet s) {
+  __shared__ double sh[6][NT];
+  const unsigned t = threadIdx.x;
+  for (unsigned unit = blockIdx.x; unit < s.n_units; unit += gridDim.x) {
+    const LpipsGradLayer l = layer_of(s, unit);
+    const unsigned rel = unit - l.first, n = rel / l.units, u = rel % l.units;
+    const unsigned px = 1u << l.px_log2, cs = NT >> l.px_log2;
+    const unsigned lane = t & (px - 1), slice = t >> l.px_log2;
+    const size_t pix = (size_t)u * px + lane;
+    const bool live = pix < l.HW;
+    const size_t base = (size_t)n * l.C * l.HW + pix;
+    const float *p0 = l.f0 + base, *p1 = l.f1 + base;
+    double a[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+    if (live) {
+#pragma unroll 4
+      for (unsigned c = slice; c < l.C; c += cs) {
+        const size_t o = (size_t)c * l.HW;
+        const double x = (double)p0[o], y = (double)p1[o], w = (double)l.w[c];
+        const double xx = x * x, yy = y * y, xy = x * y;
+        a[0] += xx, a[1] += yy, a[2] += w * xx, a[3] += w * yy, a[4] += w * xy;
+      }
+    }
+    if (cs > 1) {   // (uniform over the workgroup: the layer's geometry)
+#pragma unroll
+      for (int j = 0; j < 5; ++j) sh[j][t] = a[j];
+      __syncthreads();
+      if (slice == 0) {
+#pragma unroll
+        for (int j = 0; j < 5; ++j) {
+          double r = sh[j][lane];
+          for (unsigned q = 1; q < cs; ++q) r += sh[j][q * px + lane];
+          a[j] = r;
+        }
+      }
+    }
+    // the pixel's scalars, by slice 0 alone (the only slice where cs = 1).  A dead lane's sums are 0, so its q are
+    // 0 * inf = NaN: they are handed round like the others and never used, pass 2 skips a dead lane.
+    double v[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    if (slice == 0) {
+      const double n0 = sqrt(a[0]), n1 = sqrt(a[1]);
+      const double i0 = 1.0 / (n0 + 1e-10), i1 = 1.0 / (n1 + 1e-10);
+      const double sc = 2.0 * ((double)s.coef[n] / (double)l.HW);
+      v[0] = i0, v[1] = i1;
+      v[2] = (a[2] * i0 - a[4] * i1) * (i0 / n0);
+      v[3] = (a[3] * i1 - a[4] * i0) * (i1 / n1);
+      v[4] = sc * i0, v[5] = sc * i1;
+    }
+    if (cs > 1) {
+      // (slice 0 of a lane is the only reader of that lane's columns above, so it may overwrite column `lane` here)
+      if (slice == 0) {
+#pragma unroll
+        for (int j = 0; j < 6; ++j) sh[j][lane] = v[j];
+      }
+      __syncthreads();
+#pragma unroll
+      for (int j = 0; j < 6; ++j) v[j] = sh[j][lane];
+    }
+    if (live) {
+      float *q0 = l.g0 ? l.g0 + base : nullptr, *q1 = l.g1 ? l.g1 + base : nullptr;
+#pragma unroll 4
+      for (unsigned c = slice; c < l.C; c += cs) {
+        const size_t o = (size_t)c * l.HW;
+        const double x = (double)p0[o], y = (double)p1[o], w = (double)l.w[c];
+        const double xn = x * v[0], yn = y * v[1];
+        if (q0) q0[o] = (float)(v[4] * (w * (xn - yn) - v[2] * x));
+        if (q1) q1[o] = (float)(v[5] * (w * (yn - xn) - v[3] * y));
+      }
+    }
+    if (cs > 1) __syncthreads();   // (sh is written again in the next trip)
+  }
 }
 
 __global__ __launch_bounds__(NT) void dists_moments_kernel(const DistsSet s, double *part) {
@@ -298,6 +395,12 @@ static int launch_lpips_layers(const featmetric::LpipsSet &s, void *workspace, d
   return (int)hipGetLastError();
 }
 
+static int launch_lpips_layers_backward(const featmetric::LpipsGradSet &s, hipStream_t st) {
+  using namespace featmetric;
+  hipLaunchKernelGGL(lpips_grad_kernel, dim3(grid_of(s.n_units, tuning)), dim3(NT), 0, st, s);
+  return (int)hipGetLastError();
+}
+
 static int launch_dists_score(const featmetric::DistsSet &s, const float *alpha, const float *beta, void *workspace, double *out,
                               hipStream_t st) {
   using namespace featmetric;
@@ -343,6 +446,35 @@ int ssg_lpips_layers(int n_layers, int n_images, const size_t *f0, const size_t 
     s.l[k].f0 = (const float *)f0[k], s.l[k].f1 = (const float *)f1[k], s.l[k].w = (const float *)w[k];
   }
   return launch_lpips_layers(s, workspace, out, (hipStream_t)stream);
+}
+
+int ssg_lpips_layers_backward(int n_layers, int n_images, const size_t *f0, const size_t *f1, const size_t *w, const int *C,
+                              const int *H, const int *W, const float *coef, const size_t *grad0, const size_t *grad1,
+                              ssg_stream_t stream) {
+  using namespace featmetric;
+  LpipsSet p;
+  LpipsGradSet s;
+  if (!f0 || !f1 || !w || !coef || (!grad0 && !grad1)) return SSG_E_BADARG;
+  if (const int rc = lpips_plan(n_layers, n_images, C, H, W, &p)) return rc;
+  for (int k = 0; k < p.K; ++k) {
+    if (!f0[k] || !f1[k] || !w[k] || (grad0 && !grad0[k]) || (grad1 && !grad1[k])) return SSG_E_BADARG;
+  }
+  if (unaligned(coef, 4)) return SSG_E_ALIGN;
+  for (int k = 0; k < p.K; ++k) {
+    if (unaligned(f0[k], 4) || unaligned(f1[k], 4) || unaligned(w[k], 4) || (grad0 && unaligned(grad0[k], 4)) ||
+        (grad1 && unaligned(grad1[k], 4)))
+      return SSG_E_ALIGN;
+  }
+  s.K = p.K, s.N = p.N, s.n_units = p.n_units, s.coef = coef;
+  for (int k = 0; k < MAX_LAYERS; ++k) {
+    const int j = k < p.K ? k : 0;   // (beyond K: never selected, defined bytes for the launch)
+    const LpipsLayer &q = p.l[j];
+    LpipsGradLayer &l = s.l[k];
+    l.f0 = (const float *)f0[j], l.f1 = (const float *)f1[j], l.w = (const float *)w[j];
+    l.g0 = grad0 ? (float *)grad0[j] : nullptr, l.g1 = grad1 ? (float *)grad1[j] : nullptr;
+    l.C = q.C, l.HW = q.HW, l.first = q.first, l.units = q.units, l.px_log2 = q.px_log2;
+  }
+  return launch_lpips_layers_backward(s, (hipStream_t)stream);
 }
 
 size_t ssg_dists_workspace_bytes(int n_layers, int n_images, const int *C, const int *H, const int *W) {

@@ -7,3 +7,5 @@ from .gan_loss import GANLoss, MultiScaleGANLoss  # noqa: F401
 from .spsr import CharbonnierLoss, Get_gradient, Get_gradient_nopadding, GradientLoss, MSELoss  # noqa: F401
 from .perceptual import PerceptualLoss, VGGFeatureExtractor  # noqa: F401
 from . import kair  # noqa: F401
+from .lpips import lpips_criterion  # noqa: F401
+from .contperceptual import LPIPSWithDiscriminator  # noqa: F401

@@ -12,7 +12,8 @@ written, where the packages run 8 - 20 torch operations per layer with full-size
 
 Dispatch: fp32 GPU feature maps none of which requires a gradient take the kernels (no gradient flows through them);
 CPU tensors, fp64, half / bf16, an input that requires grad and `set_native_criteria(False)` take the packages' torch
-lines (`lpips_torch_lines`, `dists_torch_lines`) and give their bits.
+lines (`lpips_torch_lines`, `dists_torch_lines`) and give their bits.  LPIPS as a differentiable loss term is
+ssl_amd/losses/lpips.py, on `lpips_layers` and its adjoint `lpips_layers_backward` below.
 
 Differences from the reference's two functions, both where its own line cannot run: `crop_border=0` means no crop
 (its `[0:-0]` slice is an empty tensor), and `calculate_lpips(test_y_channel=True)` is refused (it would feed one
@@ -32,7 +33,7 @@ from ._gpu import address_array, launch as _launch, native, ptr as _ptr, readabl
 from .losses.perceptual import build_vgg_trunk, vgg_layer_names
 
 __all__ = ["LPIPS", "DISTS", "L2pooling", "ScalingLayer", "calculate_lpips", "calculate_dists", "lpips_dists",
-           "lpips_layers", "dists_score", "lpips_torch_lines", "dists_torch_lines", "load_lpips_weights",
+           "lpips_layers", "lpips_layers_backward", "dists_score", "lpips_torch_lines", "dists_torch_lines", "load_lpips_weights",
            "load_dists_weights", "LPIPS_WEIGHTS_ENV", "DISTS_WEIGHTS_ENV"]
 
 LPIPS_WEIGHTS_ENV = "SSL_AMD_LPIPS_WEIGHTS"
@@ -140,6 +141,35 @@ def lpips_layers(feats0, feats1, lins):
     _launch(dev, L.ssg_lpips_layers, K, N, a0.ctypes.data, a1.ctypes.data, aw.ctypes.data, C.ctypes.data, H.ctypes.data,
             W.ctypes.data, _ptr(ws), nb, _ptr(out))
     return out
+
+
+def lpips_layers_backward(feats0, feats1, lins, coef, need0=True, need1=True):
+    """ssg_lpips_layers_backward: the gradients of sum_n coef[n] * lpips_layers(...)[n, K] with respect to the maps of
+    the sides that are needed, as (grads0, grads1), each a list of K fp32 tensors shaped as its maps or None.  coef: N
+    fp32 values on the maps' GPU, any shape.  ONE launch on the current stream, no workspace, no host synchronisation.
+    It is the adjoint of the unclamped per-pixel distance; a pixel whose own vector is all zero gets NaN on that side
+    (what torch's autograd gives there)."""
+    feats0, feats1, lins = list(feats0), list(feats1), list(lins)
+    _refuse_unreadable("lpips_layers_backward", *feats0, *feats1, *lins, coef)
+    K, N, (C, H, W) = _shapes("lpips_layers_backward", feats0, feats1)
+    if not (need0 or need1):
+        raise ValueError("ssl_amd: lpips_layers_backward writes the gradient of at least one side")
+    f0, f1 = _maps(feats0), _maps(feats1)
+    w = [t.detach().contiguous().reshape(-1) for t in lins]
+    if len(w) != K or any(t.numel() != c for t, c in zip(w, C)):
+        raise ValueError("ssl_amd: lpips_layers_backward takes one weight of C_k elements per layer")
+    coef = coef.detach().contiguous().reshape(-1)
+    if coef.numel() != N:
+        raise ValueError(f"ssl_amd: lpips_layers_backward takes one coefficient per image, got {coef.numel()} for {N}")
+    dev = f0[0].device
+    g0 = [torch.empty_like(t) for t in f0] if need0 else None
+    g1 = [torch.empty_like(t) for t in f1] if need1 else None
+    a0, a1, aw = (address_array([t.data_ptr() for t in ts]) for ts in (f0, f1, w))
+    b0, b1 = (None if ts is None else address_array([t.data_ptr() for t in ts]) for ts in (g0, g1))
+    _launch(dev, _lib.lib().ssg_lpips_layers_backward, K, N, a0.ctypes.data, a1.ctypes.data, aw.ctypes.data, C.ctypes.data,
+            H.ctypes.data, W.ctypes.data, _ptr(coef), None if b0 is None else b0.ctypes.data,
+            None if b1 is None else b1.ctypes.data)
+    return g0, g1
 
 
 def dists_score(feats0, feats1, alpha, beta):
