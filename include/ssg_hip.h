@@ -87,6 +87,9 @@ typedef void *ssg_stream_t; /* hipStream_t */
 /* 6, additive once more: + ssg_adam_apply, ssg_adam_table_fill, ssg_adam_grads_fill, ssg_adam_table_bytes, the record
  * ssg_adam_scalars and SSG_ADAM_PLAIN / _L2 / _DECOUPLED (the Adam and AdamW step of a parameter group in one launch,
  * section (X)). */
+/* 6, additive once more: + ssg_sn_forward, ssg_sn_backward, ssg_sn_table_fill, ssg_sn_table_bytes, ssg_sn_output_bytes,
+ * ssg_sn_workspace_bytes, ssg_sn_saved_bytes, ssg_sn_chunk, ssg_sn_grid_cap, ssg_sn_strip, ssg_sn_rows_a, ssg_sn_rows_b
+ * (spectral normalisation of a layer set in a fixed handful of launches, section (Y)). */
 int ssg_abi_version(void);
 const char *ssg_status_string(int status);
 /* Device-side refusals that no return value can carry (everything is asynchronous): waits for `stream`, then returns
@@ -1384,6 +1387,61 @@ int ssg_adam_grads_fill(const void *table /* host */, size_t n_tensors, const si
                         size_t grads_bytes);
 int ssg_adam_apply(const void *table /* device */, const void *grads /* device */, size_t n_chunks,
                    const ssg_adam_scalars *scalars /* host */, ssg_stream_t stream);
+
+/* ---------------------------------------------------------------- (Y) ----
+ * Spectral normalisation of a whole set of layers in a fixed handful of launches, whatever the number of layers
+ * (torch.nn.utils.spectral_norm with dim = 0, n_power_iterations = 1, eps = 1e-12, as basicsr's UNetDiscriminatorSN and
+ * KAIR's Discriminator_UNet / Discriminator_PatchGAN / Discriminator_VGG_128_SN wrap their layers in it),
+ * ssl_amd/csrc/ssg_specnorm.hip.  Additive: ssg_abi_version() stays 6.  Layer l is (W, u, v): W fp32, R x K row-major
+ * (a contiguous conv weight: out x in kh kw), u (R) and v (K) fp32.  Training-mode forward:
+ *   t = W^T u      v <- (float)(t / max(|t|, eps))     stored in place and into the call's saved block
+ *   s = W v        u <- (float)(s / max(|s|, eps))     (from the fp32 v) stored in place and saved
+ *   sigma = u . s  (fp32 u, fp64 s)    sigma32 = (float)sigma saved    out = W / sigma32, one fp32 division per element
+ * Eval mode skips the two updates and uses u, v as stored (the saved block is filled all the same).  Backward, with G the
+ * gradient with respect to out:  dW = (float)((G - <G, W / sigma32> u v^T) / sigma32), in fp64 from the call's SAVED u,
+ * v and sigma32; a layer whose G address is 0 is skipped and its part of the gradient block is left as it was.
+ * Every product of two fp32 values is exact in fp64 and every sum is fp64 in an order fixed by index: the same bits from
+ * call to call, for a layer alone or among others, at any 4-byte alignment.  max(x, eps) keeps a NaN; an all-zero W
+ * gives u = v = 0 and out = NaN, as torch does.  A NaN in one layer stays in that layer.
+ * The table image (8-byte words, HOST memory from ssg_sn_table_fill, then copied to the device by the caller):
+ *   {n_layers, units of launch A, units of launch B, chunks, chunk, floats of the output block, doubles of the
+ *   workspace, floats of the saved block}; per layer eight words {W, u, v addresses, R, K, the layer's offset into the
+ *   output block (floats, a multiple of 64; the gradient block has the same layout), into the workspace (doubles), into
+ *   the saved block (floats: u, then v, then sigma32)}; three prefix tables of n_layers + 1 words (the first unit of
+ *   each layer in A, in B, and its first chunk).  The output, workspace and saved blocks are the CALLER's, per call:
+ *   ssg_sn_output_bytes, ssg_sn_workspace_bytes, ssg_sn_saved_bytes (0 where the fill would refuse the shapes).  The
+ *   workspace is only scratch between the launches of one call.
+ * ssg_sn_forward: three launches on `stream` (training) or two (eval) for `table` (the image on the device) and `image`
+ *   (the same image on the host, from which sizes and grids are read).  A unit of launch A is ssg_sn_strip() columns by
+ *   ssg_sn_rows_a() rows, of launch B ssg_sn_rows_b() rows, of launch C ssg_sn_chunk() elements; grids are capped at
+ *   ssg_sn_grid_cap() workgroups of 256 threads and walk grid-stride.  No atomics, no scratch; LDS holds the four wave
+ *   sums of a fold.  No allocation, copy, synchronisation or host read of device memory: it may be captured.
+ * ssg_sn_backward: two launches; `grads` is a DEVICE array of n_layers 8-byte words, the G addresses (0: no gradient);
+ *   `saved` the block of the forward call it belongs to; `grad` a block laid out as the output block.
+ * The caller owns what the image points to: every tensor must be alive and unmoved at each call.
+ * Status, decided before any launch with every tensor untouched: SSG_E_BADARG for a null pointer or array, R or K < 1,
+ * a training flag other than 0 or 1, a null address, or two of the 3 n_layers ranges (W, u, v) that overlap;
+ * SSG_E_ALIGN for a tensor address or block that is not 4-byte aligned, a table, image, workspace or grads array that is
+ * not 8-byte aligned; SSG_E_TOOLARGE for a layer count, a layer of 2^31 elements and more, or a unit count beyond
+ * INT_MAX; SSG_E_WORKSPACE for a table_bytes below ssg_sn_table_bytes() or an output, gradient, workspace or saved
+ * block smaller than the image says. */
+int ssg_sn_chunk(void);
+int ssg_sn_grid_cap(void);
+int ssg_sn_strip(void);
+int ssg_sn_rows_a(void);
+int ssg_sn_rows_b(void);
+size_t ssg_sn_table_bytes(size_t n_layers, const size_t *rows, const size_t *cols);
+size_t ssg_sn_output_bytes(size_t n_layers, const size_t *rows, const size_t *cols);
+size_t ssg_sn_workspace_bytes(size_t n_layers, const size_t *rows, const size_t *cols);
+size_t ssg_sn_saved_bytes(size_t n_layers, const size_t *rows, const size_t *cols);
+int ssg_sn_table_fill(size_t n_layers, const size_t *w, const size_t *u, const size_t *v, const size_t *rows,
+                      const size_t *cols, void *table /* host */, size_t table_bytes);
+int ssg_sn_forward(const void *table /* device */, const void *image /* host */, int training, float *out,
+                   size_t out_bytes, void *workspace, size_t workspace_bytes, float *saved, size_t saved_bytes,
+                   ssg_stream_t stream);
+int ssg_sn_backward(const void *table /* device */, const void *image /* host */, const void *grads /* device */,
+                    const float *saved, size_t saved_bytes, float *grad, size_t grad_bytes, void *workspace,
+                    size_t workspace_bytes, ssg_stream_t stream);
 
 #ifdef SSG_PROFILE
 /* PROFILING BUILD ONLY (libssg_hip_prof.so, compiled with -DSSG_PROFILE; the product library libssg_hip.so does not
