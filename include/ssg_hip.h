@@ -90,6 +90,8 @@ typedef void *ssg_stream_t; /* hipStream_t */
 /* 6, additive once more: + ssg_sn_forward, ssg_sn_backward, ssg_sn_table_fill, ssg_sn_table_bytes, ssg_sn_output_bytes,
  * ssg_sn_workspace_bytes, ssg_sn_saved_bytes, ssg_sn_chunk, ssg_sn_grid_cap, ssg_sn_strip, ssg_sn_rows_a, ssg_sn_rows_b
  * (spectral normalisation of a layer set in a fixed handful of launches, section (Y)). */
+/* 6, additive once more: + ssg_winattn_forward, ssg_winattn_backward, ssg_winattn_workspace_bytes, ssg_winattn_grid_cap
+ * (SwinIR's shifted-window attention between the qkv and proj Linears, section (Z)). */
 int ssg_abi_version(void);
 const char *ssg_status_string(int status);
 /* Device-side refusals that no return value can carry (everything is asynchronous): waits for `stream`, then returns
@@ -1442,6 +1444,45 @@ int ssg_sn_forward(const void *table /* device */, const void *image /* host */,
 int ssg_sn_backward(const void *table /* device */, const void *image /* host */, const void *grads /* device */,
                     const float *saved, size_t saved_bytes, float *grad, size_t grad_bytes, void *workspace,
                     size_t workspace_bytes, ssg_stream_t stream);
+
+/* ---------------------------------------------------------------- (Z) ----
+ * SwinIR's (shifted-)window attention between a block's qkv and proj Linears (GAN-Based-SR/basicsr/archs/swinir_arch.py:
+ * WindowAttention inside SwinTransformerBlock), ssl_amd/csrc/ssg_winattn.hip.  Additive: ssg_abi_version() stays 6.
+ * Window 8 (64 tokens), C = heads head_dim, 1 <= head_dim <= 32.
+ *   qkv   (B, H, W, 3 C) fp32: the qkv Linear applied to the UNPARTITIONED token grid; element
+ *         [b, y, x, (s heads + h) head_dim + c] is q, k, v for s = 0, 1, 2 (the memory of the reference's
+ *         reshape(b_, n, 3, heads, d)).  dqkv likewise.
+ *   bias_table (225, heads) fp32, the module's relative_position_bias_table; dbias_table likewise (nullable: not wanted).
+ *   out, dout (B, H, W, C) fp32, the layout proj consumes.
+ * Token (iy, ix) of window (wy, wx) has the shifted coordinate ys = 8 wy + iy, xs = 8 wx + ix and is read from and
+ * written back to ((ys + shift) mod H, (xs + shift) mod W): both rolls, the partition and the merge are index
+ * arithmetic.  Per (image, window, head), every fp32 operation rounded on its own:
+ *   S_ij = [fma chain over c of fl(q_ic scale) k_jc] + bias_table[(iy_i - iy_j + 7) 15 + (ix_i - ix_j + 7), h]
+ *          + (shift > 0: -100 where label_i != label_j, else 0), label = 3 ly + lx, ly = (ys >= H - 8) + (ys >= H - shift)
+ *          and lx likewise from xs: calculate_mask's values, with no mask tensor and no relative_position_index read;
+ *   P = softmax over j (row maximum subtracted, expf, a sum in an order fixed by index, a division);
+ *   O_ic = fma chain over j of P_ij v_jc.
+ * ssg_winattn_forward: one launch.  ssg_winattn_backward: P is recomputed from qkv (nothing is saved by the forward);
+ *   dv = P^T dO, dP = dO v^T, dS = P o (dP - rowsum(P o dP)), dq = scale dS k, dk = dS^T fl(q scale), every element of dqkv
+ *   written once (no zero-fill needed); dbias_table[idx, h] = the sum of dS_ij over the batch, the windows and the pairs
+ *   of idx, in fp64 through one partial per workgroup in `workspace` (ssg_winattn_workspace_bytes; only scratch
+ *   within the call; not read when dbias_table is NULL) and a second launch that adds them in a fixed order.
+ * A workgroup of 256 threads takes one (image, window, head); grids are capped at ssg_winattn_grid_cap() rounded down
+ * to a multiple of heads and walk grid-stride.  No atomics, no scratch, no allocation, copy or synchronisation: both
+ * may be captured.  The same bits from call to call, for an image alone or in a batch, at any 4-byte alignment; a NaN
+ * in a token stays inside its window in out and dqkv.
+ * Status, decided before any launch with the outputs untouched: SSG_E_BADARG for a null pointer (dbias_table excepted;
+ * workspace only with dbias_table), B, H, W or heads < 1, H or W no multiple of 8, shift outside 0 .. 7, head_dim
+ * outside 1 .. 32; SSG_E_ALIGN for a float pointer that is not 4-byte aligned or a workspace that is not 8-byte
+ * aligned; SSG_E_TOOLARGE for H W or a unit count beyond INT_MAX; SSG_E_WORKSPACE for workspace_bytes below
+ * ssg_winattn_workspace_bytes(...) (which is 0 for a shape that would be refused). */
+int ssg_winattn_grid_cap(void);
+size_t ssg_winattn_workspace_bytes(int B, int H, int W, int heads, int head_dim);
+int ssg_winattn_forward(const float *qkv, const float *bias_table, float *out, int B, int H, int W, int heads,
+                        int head_dim, int shift, float scale, ssg_stream_t stream);
+int ssg_winattn_backward(const float *qkv, const float *bias_table, const float *dout, float *dqkv,
+                         float *dbias_table /* nullable */, void *workspace, size_t workspace_bytes, int B, int H, int W,
+                         int heads, int head_dim, int shift, float scale, ssg_stream_t stream);
 
 #ifdef SSG_PROFILE
 /* PROFILING BUILD ONLY (libssg_hip_prof.so, compiled with -DSSG_PROFILE; the product library libssg_hip.so does not

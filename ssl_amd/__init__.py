@@ -7,7 +7,7 @@ numbers come from hand-written HIP kernels (ssl_amd/csrc) behind the C ABI in
 include/ssg_hip.h.  Importing this package does not need a GPU; computing does.
 """
 __all__ = ["similarity_map", "compute_similarity", "L1Loss", "KLDistanceLoss", "SSGLoss", "engine", "synth", "metrics",
-           "colorfix", "ema", "blindsr", "diffusion", "optim", "spectral", "archs"]
+           "colorfix", "ema", "blindsr", "diffusion", "optim", "spectral", "archs", "winattn"]
 
 
 def __getattr__(name):
@@ -18,7 +18,8 @@ def __getattr__(name):
     if name == "compute_similarity":
         from .losses.similarity.similaritywrapper import compute_similarity
         return compute_similarity
-    if name in ("engine", "synth", "metrics", "colorfix", "ema", "blindsr", "diffusion", "optim", "spectral", "archs", "_lib"):
+    if name in ("engine", "synth", "metrics", "colorfix", "ema", "blindsr", "diffusion", "optim", "spectral", "archs", "winattn",
+                "_lib"):
         import importlib
         return importlib.import_module("." + name, __name__)
     raise AttributeError(name)
